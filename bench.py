@@ -8,10 +8,13 @@ One "step" = forward (all core passes) + Focal (+10*KL) loss + backward + gradie
 fused Adam-amsgrad/L2 update, on synthetic volumes already resident in HBM.
 Rank 0 prints ONE JSON line.  The headline workload is C3 -- the north-star model: full hierarchical-probabilistic
 M1 (dense_skip, deep_supervision, latents (3,2,1,0)) on (20,160,160,3) volumes, bf16, batch 2 per GPU (C4 = the same
-on 8 GPUs); at N=1 the line also carries C2 (deterministic Attention-U-Net, same volume) under ``secondary``.
-`value` = volumes/s over all ranks; `roofline` describes the dominant kernel family (algorithmic work / hipEvent-measured
-duration on the launch stream); `cpu_baseline` is the CPU oracle (stand-in for the TF 2.5 CPU path, which cannot be
-installed) timed on this box's host cores.
+on 8 GPUs).  `value` = volumes/s over all ranks, `ms_per_step` = wall time of one timed step.
+
+A plain run sets up, warms up, times --steps steps and prints the line; `roofline` and `cpu_baseline` are null there.
+--full adds everything else the benchmark measures: `roofline` (the dominant kernel family: algorithmic work / hipEvent-
+measured duration on the launch stream, in extra eager steps), `cpu_baseline` (the CPU oracle, stand-in for the TF 2.5 CPU
+path, which cannot be installed, timed on the host cores) and, at N=1, C2 (deterministic Attention-U-Net, same volume),
+C3 in fp32 and C5 in fp32 under ``secondary``.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 import argparse
 import gc
@@ -65,7 +68,16 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="N=1, C3: do not also measure C2")
     ap.add_argument("--prof-steps", type=int, default=2)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline pass, the CPU baseline and (N=1, C3) the secondary workloads; the --no-* "
+                         "switches above apply inside --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, model outputs, a seeded sample of the "
+                         "updated parameters and of the gradients) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def ball_targets(B, dims, seed, device):
@@ -288,8 +300,25 @@ def _dbg(msg):
         print(f"[rank {os.environ.get('RANK', '0')}] {msg}", file=sys.stderr, flush=True)
 
 
-def run_workload(a, wl, ctx, want_roofline, want_cpu):
-    """Build the workload's model, time K steps, return the fields of its JSON object."""
+DUMP_MAX_ELEMS = 1 << 22          # per array: 16 MB of float32 (at most three arrays this large: detection, params, grads)
+
+
+def dump_outputs(path, arrays):
+    """Write ``{name: tensor}`` as path/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMS elements is flattened and
+    sampled at sorted indices that depend only on its size (seed 0; up to DUMP_MAX_ELEMS of them), so that two builds of the
+    same run compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        v = t.detach().float().cpu().numpy()
+        if v.size > DUMP_MAX_ELEMS:
+            v = v.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, v.size, size=DUMP_MAX_ELEMS))]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
+def run_workload(a, wl, ctx, want_roofline, want_cpu, dump_dir=None):
+    """Build the workload's model, time K steps, return the fields of its JSON object.  ``dump_dir``: write what the last timed
+    step computed there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     pkg, ops, dev, world, rank, backend, dist_on = (ctx[k] for k in ("pkg", "ops", "dev", "world", "rank", "backend", "dist_on"))
@@ -337,6 +366,7 @@ def run_workload(a, wl, ctx, want_roofline, want_cpu):
     model.train()
     loss_ref = [None]            # the loss scalar of the last executed step: a REFERENCE to the tensor the step produced (inside a captured
                                  # graph it lives in the graph's pool and is rewritten by every replay) -- no copy node in the step
+    outs_ref = [None]            # the model outputs of the last executed step, held the same way (--dump-outputs)
     # debug (harness tools only): M1_BENCH_HIST=1 records a hash of the gradient and parameter vectors after EVERY executed step
     # (eager warm-up, capture prelude, each replay) and, with M1_DEBUG_TRACE, the per-op checksum log of that step
     hist_on = os.environ.get("M1_BENCH_HIST") == "1"
@@ -359,6 +389,8 @@ def run_workload(a, wl, ctx, want_roofline, want_cpu):
         total.backward()
         opt.flatp.gather_grads()
         loss_ref[0] = total.detach()
+        if dump_dir is not None:
+            outs_ref[0] = [o.detach() for o in outs] if isinstance(outs, (list, tuple)) else [outs.detach()]
 
     def update():
         """rest of the gradient exchange (N > 1) + fused Adam-amsgrad/L2 + counters."""
@@ -488,6 +520,12 @@ def run_workload(a, wl, ctx, want_roofline, want_cpu):
                     "note": "groups are sent from the communication stream as backward completes them (ddp.py); counters "
                             "count host-side calls (in graph mode 'full' the captured collectives replay without them)"}
     final_loss = float(loss_ref[0])
+    if dump_dir is not None and rank == 0:
+        # what a caller of the step receives: the loss, the model outputs and the updated parameters (+ the step's gradients)
+        names = ["detection", "kl"] if prob else ["detection"]
+        n = opt.flatp.n
+        dump_outputs(dump_dir, dict(loss=loss_ref[0], **dict(zip(names, outs_ref[0])),
+                                    params=opt.flatp.flat[:n], grads=opt.flatp.grad[:n]))
     if os.environ.get("M1_BENCH_TORCH_OPS") and rank == 0:
         # debug: which torch-side (non-library) device ops one eager step issues, and from which line of this repository
         import collections
@@ -726,8 +764,9 @@ def main():
         globals()["_PAD"] = [torch.empty(int(float(v) * (1 << 20)), dtype=torch.uint8, device=dev) for v in os.environ["M1_BENCH_PAD_MB"].split(",")]
     ctx = dict(pkg=pkg, ops=ops, dev=dev, world=world, rank=rank, backend=backend, dist_on=dist_on)
 
-    out = run_workload(a, a.workload, ctx, want_roofline=not a.no_roofline, want_cpu=(not a.no_cpu_baseline and not dist_on))
-    if a.workload == "C3" and not dist_on and not a.no_secondary and a.batch is None:
+    out = run_workload(a, a.workload, ctx, want_roofline=a.full and not a.no_roofline,
+                       want_cpu=a.full and not a.no_cpu_baseline and not dist_on, dump_dir=a.dump_outputs)
+    if a.full and a.workload == "C3" and not dist_on and not a.no_secondary and a.batch is None:
         # the light deterministic variant of the same volume (BASELINE.json configs[1]) next to the headline
         keys = ("value", "unit", "ms_per_step", "dtype", "config", "roofline")
         sec = run_workload(a, "C2", ctx, want_roofline=not a.no_roofline, want_cpu=False)

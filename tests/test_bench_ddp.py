@@ -80,7 +80,7 @@ def test_bench_two_ranks_one_gpu_gloo(gmode):
     env = dict(os.environ, M1_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", M1_BENCH_DEBUG="1", M1_DDP_GRAPH=gmode)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "C1", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-cpu-baseline"]
     rc, out, err = _run_retrying_bringup(cmd, env, "--master-port")
     d = _check_line(rc, out, err, 2)
     ex = d["config"]["exchange"]
@@ -99,7 +99,7 @@ def test_bench_rccl_world_of_one(rs_ag):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29534", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                M1_BENCH_FORCE_DIST="1", M1_BENCH_DEBUG="1", M1_DDP_RSAG=rs_ag)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "C1", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     rc, out, err = _run_retrying_bringup(cmd, env)
     d = _check_line(rc, out, err, 1)
     ex = d["config"]["exchange"]
@@ -238,7 +238,7 @@ def test_bench_gpus_2_without_torchrun_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(M1_BENCH_BACKEND="gloo", M1_BENCH_DEBUG="1", M1_DDP_GRAPH="off", MASTER_PORT="29541")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "C1", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     rc, out, err = _run_retrying_bringup(cmd, env)
     d = _check_line(rc, out, err, 2)
     assert d["config"]["exchange"]["replicas_in_sync"] is True and d["config"]["parallelism"] == "dp2"

@@ -70,8 +70,8 @@ def test_no_register_of_an_inline_asm_load_is_touched_in_flight(src):
         open(planted, "w").write("_Zk:\n\t;;#ASMSTART\n\tds_read_b128 v[4:7], v1\n\t;;#ASMEND\n\tv_mov_b32_e32 v9, v5\n\t;;#ASMSTART\n"
                                  "\ts_waitcnt lgkmcnt(0)\n\t;;#ASMEND\n\tv_mov_b32_e32 v10, v6\n\ts_endpgm\n")
         assert len(chk.check_file(planted)) == 1
-    out = chk.compile_s(os.path.join(CSRC, src), chk.makefile_flags())
-    kernels = chk.split_kernels(out)
-    n_asm_reads = sum(1 for v in kernels.values() for it in v if it[1] != "label" and it[2] and it[1].startswith("ds_read"))
-    assert n_asm_reads > 100 or src in ("wgrad_t3.hip", "wgrad_t3s.hip")      # (their fragment reads are compiler-visible; their inline asm is the LDS-DMA, checked for M0)
-    assert chk.check_file(out) == []
+        out = chk.compile_s(os.path.join(CSRC, src), chk.makefile_flags(), os.path.join(td, src + ".s"))
+        kernels = chk.split_kernels(out)
+        n_asm_reads = sum(1 for v in kernels.values() for it in v if it[1] != "label" and it[2] and it[1].startswith("ds_read"))
+        assert n_asm_reads > 100 or src in ("wgrad_t3.hip", "wgrad_t3s.hip")      # (their fragment reads are compiler-visible; their inline asm is the LDS-DMA, checked for M0)
+        assert chk.check_file(out) == []

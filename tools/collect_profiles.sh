@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-r03}; QUICK=$2; O=$R/gpurun_out/prof_$TAG
 cd /tmp; export TMPDIR=/tmp
 for WL in ${WLS:-C3 C2 C5}; do
   wl=${WL,,}; DT=bf16; [ $WL = C5 ] && DT=fp32; BV=2; [ $WL = C5 ] && BV=1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$WL -- python3 $R/bench.py --workload $WL --no-secondary --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$WL.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$WL -- python3 $R/bench.py --workload $WL --full --no-secondary --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$WL.log 2>&1
   f=$(ls $O/kt_$WL/*/*kernel_stats.csv | head -1); cp $f $O/${TAG}_${wl}_${DT}_kernel_stats.csv
   t=$(ls $O/kt_$WL/*/*kernel_trace.csv | head -1)
   python3 $R/tools/prof_table.py $t 1 70 > $O/${TAG}_${wl}_${DT}_by_grid_total.txt

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 for cfg in "$@"; do
   echo "== $cfg"
-  env $cfg python bench.py --workload ${WL:-C3} --no-secondary --no-cpu-baseline --steps ${STEPS:-20} --warmup 5 2>/dev/null | python -c "
+  env $cfg python bench.py --workload ${WL:-C3} --full --no-secondary --no-cpu-baseline --steps ${STEPS:-20} --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline'] or {}

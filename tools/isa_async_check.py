@@ -45,8 +45,8 @@ def makefile_flags():
     return ["-O3", "-std=c++17", "--offload-arch=gfx950"] + nopk
 
 
-def compile_s(src, flags):
-    out = f"/tmp/isa_check_{os.path.basename(src)}.s"
+def compile_s(src, flags, out=None):
+    out = out or f"/tmp/isa_check_{os.path.basename(src)}.s"
     subprocess.run([HIPCC, "-S", "--cuda-device-only", *flags, "-o", out, os.path.abspath(src)], check=True, cwd=CSRC, stderr=subprocess.DEVNULL)
     return out
 
