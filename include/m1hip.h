@@ -324,6 +324,24 @@ int m1_focal_fwd(const float* probs, const void* y_true, int y_dtype, const floa
 int m1_focal_bwd(const float* probs, const void* y_true, int y_dtype, const float* alpha, float gamma, int N, long long V,
                  int nheads, int nc, const float* dloss, float* dprobs, void* stream);
 
+/* ---- Soft Dice + Boundary (surface) loss on the softmax heads : losses.py:66-130 (SoftDicePlusBoundarySurface) ----
+ * Distance map (calc_dist_map, L:83-92): y_true (N,D,H,W,nc) fp32 or bf16 one-hot, nc >= 2; for each sample and class c >= 1,
+ * pos = (y_true[...,c] != 0): phi = edt(~pos) on ~pos, 1 - edt(pos) on pos (exact Euclidean distance, unit spacing); phi = 0 for
+ * a class with no foreground voxel in the sample (L:90) and for one with no background voxel (where scipy is degenerate).
+ * out: phi (N,D,H,W,nc-1) fp32.  ws: m1_dist_map_ws_bytes bytes.  D, H, W <= 256, nc <= 8 (M1_ERR_UNSUPPORTED otherwise).
+ * Loss (DB + loss, L:94-130): probs (NV, nheads*nc) fp32 as written by m1_softmax_heads_fwd, y_true (NV,nc), phi (NV,nc-1);
+ *   per head: q = clip(p / sum p, 1e-7, 1-1e-7), I = sum y q, Dn = sum (y + q), B = sum q phi over every voxel and class >= 1
+ *   of the whole batch; loss = mean_h [w0 (1 - 2 I / (Dn + smooth)) + w1 B].
+ * fwd: ws of m1_dice_bd_ws_floats floats, 8-byte aligned (fp64 per-block partials folded in a fixed order; I and Dn stay there
+ * for the backward); loss: 1 device float.  bwd: the same ws after fwd; dprobs = dloss[0] * dLoss/dprobs. */
+size_t m1_dist_map_ws_bytes(int N, int D, int H, int W, int nc);
+int m1_dist_map(const void* y_true, int y_dtype, int N, int D, int H, int W, int nc, void* ws, float* out, void* stream);
+size_t m1_dice_bd_ws_floats(long long NV, int nheads);
+int m1_dice_bd_fwd(const float* probs, const void* y_true, int y_dtype, const float* phi, long long NV, int nheads, int nc,
+                   float w0, float w1, float smooth, float* ws, float* loss, void* stream);
+int m1_dice_bd_bwd(const float* probs, const void* y_true, int y_dtype, const float* phi, long long NV, int nheads, int nc,
+                   float w0, float w1, float smooth, const float* ws, const float* dloss, float* dprobs, void* stream);
+
 /* ---- MonteCarloDropout / Dropout : B:142-143 ; N:462-463 (Philox4x32-10, mask regenerated in bwd) ---- */
 int m1_dropout(const void* x, void* y, long long n, float rate, const uint64_t* rng, uint64_t layer_id, int dtype,
                void* stream);

@@ -116,6 +116,11 @@ SIGNATURES = {
     "m1_focal_ws_floats": (_sz, [_i, _ll, _i]),
     "m1_focal_fwd": (_i, [_vp, _vp, _i, C.POINTER(_f), _f, _i, _ll, _i, _i, _vp, _vp, _vp]),
     "m1_focal_bwd": (_i, [_vp, _vp, _i, C.POINTER(_f), _f, _i, _ll, _i, _i, _vp, _vp, _vp]),
+    "m1_dist_map_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "m1_dist_map": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "m1_dice_bd_ws_floats": (_sz, [_ll, _i]),
+    "m1_dice_bd_fwd": (_i, [_vp, _vp, _i, _vp, _ll, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
+    "m1_dice_bd_bwd": (_i, [_vp, _vp, _i, _vp, _ll, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "m1_dropout": (_i, [_vp, _vp, _ll, _f, _vp, _u64, _i, _vp]),
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),

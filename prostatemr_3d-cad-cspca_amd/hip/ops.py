@@ -1513,6 +1513,66 @@ def focal_loss(y_true: torch.Tensor, y_pred: torch.Tensor, alpha: Sequence[float
     return _Focal.apply(y_true.contiguous(), y_pred.contiguous(), tuple(float(a) for a in alpha), float(gamma))
 
 
+def _label_dtype(y_true: torch.Tensor) -> torch.Tensor:
+    return y_true if y_true.dtype in (torch.float32, torch.bfloat16) else y_true.to(torch.float32)
+
+
+def dist_map(y_true: torch.Tensor) -> torch.Tensor:
+    """SoftDicePlusBoundarySurface.calc_dist_map_batch (losses.py:83-97) of the foreground classes: y_true (N,D,H,W,nc) one-hot
+    -> signed Euclidean distance map phi (N,D,H,W,nc-1) fp32 (m1_dist_map; dice_boundary.hip).  No autograd: phi is a label."""
+    _req(y_true)
+    if y_true.dim() != 5 or int(y_true.shape[-1]) < 2:
+        raise RuntimeError("dist_map: y_true must be (N,D,H,W,nc) with nc >= 2 (class 0 is the background)")
+    y_true = _label_dtype(y_true).contiguous()
+    N, D, H, W, nc = (int(v) for v in y_true.shape)
+    lib = L.load()
+    ws = torch.empty(max(int(lib.m1_dist_map_ws_bytes(N, D, H, W, nc)), 1), dtype=torch.uint8, device=y_true.device)
+    out = torch.empty((N, D, H, W, nc - 1), dtype=torch.float32, device=y_true.device)
+    L.check(lib.m1_dist_map(_p(y_true), _dt(y_true), N, D, H, W, nc, _p(ws), _p(out), _stream()), "m1_dist_map")
+    return out
+
+
+class _DiceBoundary(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y_true, y_pred, w0, w1, smooth):
+        _req(y_true, y_pred)
+        if y_pred.dtype != torch.float32:
+            raise RuntimeError("dice_boundary_loss: y_pred must be the fp32 probabilities of softmax_heads")
+        nc = int(y_true.shape[-1])
+        nheads = int(y_pred.shape[-1]) // nc
+        if nheads * nc != int(y_pred.shape[-1]) or y_true.shape[:-1] != y_pred.shape[:-1] or y_true.dim() != 5:
+            raise RuntimeError("dice_boundary_loss: y_pred must hold nheads*nc channels over the (N,D,H,W) voxels of y_true")
+        y_true = _label_dtype(y_true)
+        phi = dist_map(y_true)
+        NV = y_true.numel() // nc
+        lib = L.load()
+        ws = torch.empty(max(int(lib.m1_dice_bd_ws_floats(NV, nheads)), 2), dtype=torch.float32, device=y_pred.device)
+        loss = torch.empty((), dtype=torch.float32, device=y_pred.device)
+        L.check(lib.m1_dice_bd_fwd(_p(y_pred), _p(y_true), _dt(y_true), _p(phi), NV, nheads, nc, w0, w1, smooth, _p(ws), _p(loss),
+                                   _stream()), "m1_dice_bd_fwd")
+        ctx.save_for_backward(y_true, y_pred, phi, ws)
+        ctx.cfg = (NV, nheads, nc, w0, w1, smooth)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        y_true, y_pred, phi, ws = ctx.saved_tensors
+        NV, nheads, nc, w0, w1, smooth = ctx.cfg
+        dloss = dloss.contiguous().float()
+        dp = torch.empty_like(y_pred)
+        L.check(L.load().m1_dice_bd_bwd(_p(y_pred), _p(y_true), _dt(y_true), _p(phi), NV, nheads, nc, w0, w1, smooth, _p(ws),
+                                        _p(dloss), _p(dp), _stream()), "m1_dice_bd_bwd")
+        return None, dp, None, None, None
+
+
+def dice_boundary_loss(y_true: torch.Tensor, y_pred: torch.Tensor, weights: Sequence[float], smooth: float) -> torch.Tensor:
+    """SoftDicePlusBoundarySurface.loss (losses.py:66-130) over all heads of ``y_pred``: the distance map of ``y_true`` once per
+    call, then one fused forward pass (m1_dice_bd_fwd / m1_dice_bd_bwd); gradient w.r.t. ``y_pred`` only."""
+    if len(weights) != 2:
+        raise RuntimeError("dice_boundary_loss: weights must be [dice weight, boundary weight]")
+    return _DiceBoundary.apply(y_true.contiguous(), y_pred.contiguous(), float(weights[0]), float(weights[1]), float(smooth))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # dropout (standalone), cast
 # ---------------------------------------------------------------------------------------------------------

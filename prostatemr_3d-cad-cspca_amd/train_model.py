@@ -14,7 +14,9 @@ What differs from the reference, and why (its harness bugs a
   * multi-GPU: one process per GPU under torchrun + RCCL all-reduce (ddp.py) instead of ``--GPU_DEVICE_IDs`` +
     tf.distribute.MirroredStrategy inside one process (T:167-170); the flag is accepted and must agree with WORLD_SIZE.
   * ``--LR_MODE CLR`` refers to a CyclicLR the reference never imports (T:247-251): not offered.  ``--OPTIMIZER momentum``
-    (T:121) and ``--LOSS_MODE region_boundary`` (T:125, CPU distance transforms) are outside the hot path: rejected loudly.
+    (T:121) is outside the hot path: rejected loudly.  ``--LOSS_MODE region_boundary`` (T:125) trains with
+    ``losses.SoftDicePlusBoundarySurface`` (GPU distance transform, no CPU step); under data parallelism each rank takes the
+    loss of its own shard and the gradient all-reduce averages it, as MirroredStrategy does per replica.
   * checkpoints are ``model_weights_NNN.npz`` (callbacks.py); the fold-finished test uses the intended file name
     (the reference formats a set literal into it, T:103).
 """
@@ -209,11 +211,14 @@ def train_fold(args, f: int, device, rank: int = 0, world: int = 1):
         raise NotImplementedError("only --OPTIMIZER adam (Adam amsgrad, train_model.py:120) runs on the fused HIP optimiser")
     OPTIMIZER_SET = optim.Adam(learning_rate=BASE_LR, amsgrad=True)
     # Losses (T:124-131)
-    if args.LOSS_MODE != 'distribution_focal':
-        raise NotImplementedError("--LOSS_MODE region_boundary needs CPU distance transforms (losses.py:66-130): out of scope")
-    if len(args.FOCAL_LOSS_ALPHA) != NUM_CLASSES:                               # T:154-155
-        raise Exception("Number of Class Weights Declared in Loss Function != Number of Classes in Labels/Loss Objective")
-    LOSSES = [losses.Focal(alpha=args.FOCAL_LOSS_ALPHA, gamma=args.FOCAL_LOSS_GAMMA).loss]
+    if args.LOSS_MODE == 'distribution_focal':
+        if len(args.FOCAL_LOSS_ALPHA) != NUM_CLASSES:                           # T:154-155
+            raise Exception("Number of Class Weights Declared in Loss Function != Number of Classes in Labels/Loss Objective")
+        LOSSES = [losses.Focal(alpha=args.FOCAL_LOSS_ALPHA, gamma=args.FOCAL_LOSS_GAMMA).loss]
+    elif args.LOSS_MODE == 'region_boundary':
+        LOSSES = [losses.SoftDicePlusBoundarySurface(loss_weights=args.DSC_BD_LOSS_WEIGHTS).loss]
+    else:
+        raise NotImplementedError(f"--LOSS_MODE {args.LOSS_MODE!r}: 'distribution_focal' or 'region_boundary' (train_model.py:124-125)")
     LOSS_WEIGHTS = [1.00]
     if prob:
         LOSSES += [losses.EvidenceLowerBound().loss]
