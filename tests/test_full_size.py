@@ -248,12 +248,9 @@ def test_full_size_c3_model_properties(dev):
     assert torch.equal(p1, p2) and kl1 == kl2 and l1 == l2
 
 
-def test_full_size_c3_bench_configuration_batch2_dropout(dev):
-    """The exact configuration bench.py times, at full size: C3, bf16, batch 2 (the four passes stacked into two of batch 4), Monte-Carlo
-    dropout 0.5 (0.25 behind sersd0), flat gradient buffers, drawn latents.  Properties: finite loss and gradients, KL >= 0, output
-    simplex, layers no training output reads get exactly no gradient, and the same (seed, step) gives the same step bit for bit
-    while another step counter gives another dropout draw."""
-    dims = (20, 160, 160)
+def c3_bench_model(dev, dims=(20, 160, 160)):
+    """The model of bench.py's C3 configuration: full hierarchical-probabilistic M1, bf16, Monte-Carlo dropout 0.5 (0.25 behind
+    sersd0), seeded dropout stream.  (Also used by test_ops_at_scale.py to record the shapes the step calls its non-conv ops at.)"""
     init = PKG.initializers
     PKG.unets.network_blocks.set_init_seed(0)
     m = PKG.unets.networks.M1(
@@ -266,6 +263,16 @@ def test_full_size_c3_bench_configuration_batch2_dropout(dev):
         deep_supervision=True, probabilistic=True, summary=False).to(dev)
     m.set_compute_dtype(torch.bfloat16)
     m.seed_dropout(3)
+    return m
+
+
+def test_full_size_c3_bench_configuration_batch2_dropout(dev):
+    """The exact configuration bench.py times, at full size: C3, bf16, batch 2 (the four passes stacked into two of batch 4), Monte-Carlo
+    dropout 0.5 (0.25 behind sersd0), flat gradient buffers, drawn latents.  Properties: finite loss and gradients, KL >= 0, output
+    simplex, layers no training output reads get exactly no gradient, and the same (seed, step) gives the same step bit for bit
+    while another step counter gives another dropout draw."""
+    dims = (20, 160, 160)
+    m = c3_bench_model(dev)
     assert m.m1_model.stack_passes
     tgt = torch.cat([_box_target(dims), _box_target(dims).roll(17, dims=2)], dim=0)
     x = rnd((2, *dims, 3), 11)

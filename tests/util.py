@@ -156,3 +156,185 @@ class activation_pattern:
         dm = {tag: {k: m.to(dtype) for k, m in per.items()} for tag, per in self.drop.items()}
         dm["__keep_all_where_missing__"] = True
         return dm
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# fp64 references of the non-conv ops, device-agnostic (they run where their inputs live: on the GPU at the bench step's own sizes,
+# where the CPU oracle would take minutes), written with plain tensor algebra only -- the 1x1x1 SE-gate and psi convolutions are
+# einsum / matmul, not conv3d.  Backward passes come from autograd.  tests/test_ops_at_scale.py pins each one to oracle/m1_oracle.py.
+# ---------------------------------------------------------------------------------------------------------------------------------
+IN_EPS64 = 1e-3
+LRELU64 = 0.1
+
+
+def ref_in_stats(x: torch.Tensor) -> torch.Tensor:
+    """(N, C, 2) {mean, rstd} of an NDHWC tensor over D, H, W (biased variance, eps 1e-3), fp64."""
+    x = x.double()
+    mu = x.mean(dim=(1, 2, 3))
+    var = ((x - mu[:, None, None, None]) ** 2).mean(dim=(1, 2, 3))
+    return torch.stack([mu, torch.rsqrt(var + IN_EPS64)], dim=-1)
+
+
+def ref_instnorm(x, gamma, beta):
+    mu = x.mean(dim=(1, 2, 3), keepdim=True)
+    var = ((x - mu) ** 2).mean(dim=(1, 2, 3), keepdim=True)
+    return (x - mu) * torch.rsqrt(var + IN_EPS64) * gamma + beta
+
+
+def ref_lrelu(x, slope=LRELU64):
+    return torch.where(x >= 0, x, slope * x)
+
+
+def ref_instnorm_act(x, gamma, beta, slope):
+    return ref_lrelu(ref_instnorm(x, gamma, beta), slope)
+
+
+def ref_se_gate(x_, W6, b6, W7, b7):
+    """sigmoid(W7 . lrelu(W6 . GAP(x_) + b6) + b7) per sample: (N, 1, 1, 1, F); W6 (1,1,1,F,Fr), W7 (1,1,1,Fr,F)."""
+    gp = x_.mean(dim=(1, 2, 3))
+    h = ref_lrelu(gp @ W6.reshape(W6.shape[-2], W6.shape[-1]) + b6)
+    return torch.sigmoid(h @ W7.reshape(W7.shape[-2], W7.shape[-1]) + b7)[:, None, None, None, :]
+
+
+def ref_se_combine(y3, y4, g3, b3, g4, b4, W6, b6, W7, b7, rate=0.0, keep=None, dup=False, inter=None):
+    """dropout(lrelu(IN3(y3) * gate * R)), R = IN4(y4) (member residual) or y4 itself (identity residual: g4 = b4 = None).
+    ``dup``: two output samples per input sample, n and n + N, each behind its own slice of ``keep`` (shape of the output).
+    ``inter`` (a dict): receives the intermediate tensors x_ (IN3 output), rho, gate and prod (= x_ * gate * rho), their gradients
+    retained (the terms of the parameter gradients' sums)."""
+    x_ = ref_instnorm(y3, g3, b3)
+    rho = y4 if g4 is None else ref_instnorm(y4, g4, b4)
+    gate = ref_se_gate(x_, W6, b6, W7, b7)
+    prod = x_ * gate * rho
+    if inter is not None:
+        for k, t in (("x_", x_), ("rho", rho), ("gate", gate), ("prod", prod)):
+            if t.requires_grad:
+                t.retain_grad()
+            inter[k] = t
+    out = ref_lrelu(prod)
+    if dup:
+        out = torch.cat([out, out], dim=0)
+    if rate > 0.0:
+        out = out * keep.to(out.dtype) / (1.0 - rate)
+    return out
+
+
+def ref_upsample(x, size):
+    for ax, r in enumerate(size):
+        if int(r) != 1:
+            x = x.repeat_interleave(int(r), dim=1 + ax)
+    return x
+
+
+def ref_gate_sigma(theta, phi, wpsi, bpsi):
+    """sigmoid(psi(lrelu(theta + up(phi)))): (N, Dt, Ht, Wt); psi as a contraction over the channels."""
+    up = [t // p for t, p in zip(theta.shape[1:4], phi.shape[1:4])]
+    f = ref_lrelu(theta + ref_upsample(phi, up))
+    return torch.sigmoid(torch.einsum("ndhwc,c->ndhw", f, wpsi.reshape(-1)) + bpsi.reshape(()))
+
+
+def ref_gate_sigma_mul(theta, phi, wpsi, bpsi, x, ss, sigma_dtype=None):
+    """(y, sigma), y = up(sigma, ss) * x.  ``sigma_dtype``: the product reads sigma as stored in that type (the value rounded, the
+    gradient passed straight through), as the kernels do."""
+    if sigma_dtype is None or sigma_dtype == torch.float64:
+        sg = ref_gate_sigma(theta, phi, wpsi, bpsi)
+    else:
+        # the backward kernels read the STORED sigma and d(sigma): d(psi) = round(d sigma) * s_r * (1 - s_r), s_r = round(sigma)
+        up = [t // p for t, p in zip(theta.shape[1:4], phi.shape[1:4])]
+        psi = torch.einsum("ndhwc,c->ndhw", ref_lrelu(theta + ref_upsample(phi, up)), wpsi.reshape(-1)) + bpsi.reshape(())
+        s_r = torch.sigmoid(psi.detach()).to(sigma_dtype).double()
+        sg = _RoundGrad.apply(s_r + (psi - psi.detach()) * s_r * (1 - s_r), sigma_dtype)
+    return ref_upsample(sg.unsqueeze(-1), ss) * x, sg
+
+
+def ref_pointwise_conv(x, w, b):
+    """1x1x1 convolution NDHWC (Cin) -> (Cout) as a contraction; w (1, 1, 1, Cin, Cout)."""
+    return torch.einsum("ndhwc,co->ndhwo", x, w.reshape(w.shape[-2], w.shape[-1])) + b
+
+
+def round_grad(x, dtype):
+    """Identity whose backward rounds the gradient to ``dtype``: a data gradient a kernel stores in that type."""
+    return x if dtype in (None, torch.float64, torch.float32) else _RoundGrad.apply(x, dtype)
+
+
+class _RoundGrad(torch.autograd.Function):
+    """Identity whose backward rounds the incoming gradient to ``dtype`` (a gradient the kernels store in that type)."""
+    @staticmethod
+    def forward(ctx, x, dtype):
+        ctx.dtype = dtype
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(ctx.dtype).to(g.dtype), None
+
+
+def ref_softmax_heads(logits, ups):
+    return torch.cat([torch.softmax(ref_upsample(t, u), dim=-1) for t, u in zip(logits, ups)], dim=-1)
+
+
+def ref_focal_terms(y_true, y_pred, alpha, gamma):
+    """Per (voxel, head) focal terms (N, D, H, W, nheads) of losses.py Focal.FL: the loss is their sum over voxels, mean over samples
+    and heads."""
+    nc = y_true.shape[-1]
+    nh = y_pred.shape[-1] // nc
+    p = y_pred.reshape(*y_pred.shape[:-1], nh, nc)
+    p = torch.clamp(p / p.sum(dim=-1, keepdim=True), 1e-7, 1 - 1e-7)
+    y = y_true.unsqueeze(-2).to(p.dtype)
+    cw = torch.tensor(alpha, dtype=p.dtype, device=p.device)
+    return (cw * ((y * torch.pow(1.0 - p, gamma)) * (y * -torch.log(p)))).sum(dim=-1)
+
+
+def ref_focal(y_true, y_pred, alpha, gamma):
+    t = ref_focal_terms(y_true, y_pred, alpha, gamma)
+    return t.sum(dim=(1, 2, 3)).mean()
+
+
+def ref_latent_sample(ml, eps):
+    L_ = ml.shape[-1] // 2
+    return ml[..., :L_] + torch.exp(torch.clamp(ml[..., L_:], -0.1, 0.1)) * eps
+
+
+def ref_kl_terms(mq, mp, first=None):
+    """Per-voxel KL(q || p) of the first ``first`` samples (N', D, H, W); log-sigma clipped to +-0.1."""
+    n = mq.shape[0] if first is None else int(first)
+    mq, mp = mq[:n], mp[:n]
+    L_ = mq.shape[-1] // 2
+    lq, lp = torch.clamp(mq[..., L_:], -0.1, 0.1), torch.clamp(mp[..., L_:], -0.1, 0.1)
+    t = torch.exp(2 * (lq - lp)) + ((mq[..., :L_] - mp[..., :L_]) / torch.exp(lp)) ** 2 - 1.0 + 2.0 * (lp - lq)
+    return 0.5 * t.sum(dim=-1)
+
+
+def ref_kl(mq, mp, first=None):
+    return ref_kl_terms(mq, mp, first).sum(dim=(1, 2, 3)).mean().reshape(1)
+
+
+def ref_adam_amsgrad_step(p, g, m, v, vhat, t, n_kernel, n_bias, l2k, l2b, grad_scale, lr, b1, b2, eps):
+    """One Keras Adam(amsgrad) step with the L2 gradient 2*lambda*w on the [kernels | biases | rest] ranges; returns (p, m, v, vhat)."""
+    lam = torch.zeros_like(p)
+    lam[:n_kernel] = l2k
+    lam[n_kernel:n_kernel + n_bias] = l2b
+    gr = grad_scale * g + 2.0 * lam * p
+    m = b1 * m + (1 - b1) * gr
+    v = b2 * v + (1 - b2) * gr * gr
+    vhat = torch.maximum(vhat, v)
+    lr_t = lr * (1 - b2 ** t) ** 0.5 / (1 - b1 ** t)
+    return p - lr_t * m / (vhat.sqrt() + eps), m, v, vhat
+
+
+def assert_close_ew(got: torch.Tensor, ref: torch.Tensor, a: float, b: float, mag=None, what: str = ""):
+    """Per element |got - ref| <= a*mag + b*rms(ref), mag = |ref| unless given (e.g. the sum of |terms| behind each element);
+    evaluated where the tensors live.  Reports the worst element (by excess over its bound) and its index."""
+    got = got.detach(); ref = ref.detach()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    r = ref.double()
+    d = (got.double() - r).abs()
+    rms = float(r.square().mean().sqrt()) if r.numel() else 0.0
+    bound = a * (r.abs() if mag is None else mag.double()) + b * rms
+    excess = d - bound
+    k = int(torch.argmax(excess))
+    if not (float(excess.reshape(-1)[k]) <= 0.0 and bool(torch.isfinite(got).all())):
+        idx = tuple(int(i) for i in np.unravel_index(k, tuple(got.shape)))
+        nbad = int((excess > 0).sum()) + int((~torch.isfinite(got)).sum())
+        raise AssertionError(f"{what}: {nbad} of {got.numel()} elements outside |d| <= {a:.3g}*|ref| + {b:.3g}*rms; worst at {idx}: "
+                             f"got {float(got.reshape(-1)[k]):.9g} ref {float(r.reshape(-1)[k]):.9g} bound {float(bound.reshape(-1)[k]):.3g} "
+                             f"(rms(ref) {rms:.3g})")
