@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import m1_oracle as O
-from util import PKG, ops, rel_err, rnd
+from util import PKG, ops, rel_err, rnd, assert_conv_close, ref_conv_with_mag, ref_member_amag
 
 pytestmark = pytest.mark.gpu
 
@@ -981,7 +981,7 @@ def _t3_fp32_wgrad_case(dev, case):
     dims, cins, cout, k = case
     s = (1, 1, 1)
     xs = [rnd((*dims, c), 50 + i) for i, c in enumerate(cins)]
-    w = rnd((*k, sum(cins), cout), 6, 1.0 / (sum(cins) * k[0] * k[1] * k[2]) ** 0.5); b = rnd((cout,), 7)
+    w = rnd((*k, sum(cins), cout), 6, 1.0 / (sum(cins) * k[0] * k[1] * k[2]) ** 0.5).bfloat16().float(); b = rnd((cout,), 7)
     yo = O.conv3d_same(torch.cat(xs, -1).double(), w.double(), b.double(), s)
     dy = rnd(tuple(yo.shape), 8)
     yo, (gx, gw, gb) = _oracle_grads(lambda x, w_, b_: O.conv3d_same(x, w_, b_, s), [torch.cat(xs, -1), w, b], dy)
@@ -1114,7 +1114,7 @@ def test_conv_t3_staged_run_kernel(dev, case):
     dims, cins, cout, k, extra = case
     s = (1, 1, 1)
     xs = [rnd((*dims, c), 70 + i).bfloat16().float() for i, c in enumerate(cins)]
-    w = rnd((*k, sum(cins), cout), 6, 1.0 / (sum(cins) * k[0] * k[1] * k[2]) ** 0.5); b = rnd((cout,), 7)
+    w = rnd((*k, sum(cins), cout), 6, 1.0 / (sum(cins) * k[0] * k[1] * k[2]) ** 0.5).bfloat16().float(); b = rnd((cout,), 7)
     yo = O.conv3d_same(torch.cat(xs, -1).double(), w.double(), b.double(), s)
     dy = rnd(tuple(yo.shape), 8).bfloat16().float()
     yo, (gx, gw, gb) = _oracle_grads(lambda x, w_, b_: O.conv3d_same(x, w_, b_, s), [torch.cat(xs, -1), w, b], dy)
@@ -1126,7 +1126,7 @@ def test_conv_t3_staged_run_kernel(dev, case):
             y, st = ops.conv3d_same(xd, wd, bd, k, s, stats=True)
             y.backward(dy.to(dev, torch.bfloat16))
             torch.cuda.synchronize()
-            res[tag] = (y.detach(), st, [x.grad for x in xd], wd.grad)
+            res[tag] = (y.detach(), st, [x.grad for x in xd], wd.grad, bd.grad)
         # the staged-run kernel must have taken BOTH the forward and the data gradient (m1_ct3_plan has a dozen decline conditions: a
         # declined shape would compare conv_mfma with conv_mfma), on the forced tile width; the other arm must not touch it
         t3 = [n for n in kl.names if n.startswith("conv_t3:")]
@@ -1139,7 +1139,17 @@ def test_conv_t3_staged_run_kernel(dev, case):
                 assert all(n.endswith(f":ks{extra['M1_CT3_KSPLIT']}") for n in t3), kl.names
         else:
             assert not t3, kl.names
-    y, st, gxd, gwd = res["t3"]
+    y, st, gxd, gwd, gbd = res["t3"]
+    # per element against the sum of |terms| (one launch each for the forward and the data gradient: one rounding of the bf16 result)
+    _, mg = ref_conv_with_mag(torch.cat(xs, -1), w, b, s, dy)
+    assert_conv_close(y.cpu(), yo, mg["y"], torch.bfloat16, f"y of {case}")
+    off = 0
+    for x, g in zip(xs, gxd):
+        c = x.shape[-1]
+        assert_conv_close(g.cpu(), gx[..., off:off + c], mg["dx"][..., off:off + c], torch.bfloat16, f"dx[{off}] of {case}")
+        off += c
+    assert_conv_close(gwd.cpu(), gw, mg["dw"], torch.float32, f"dW of {case}")
+    assert_conv_close(gbd.cpu(), gb, mg["db"], torch.float32, f"db of {case}")
     tol = 1e-2                                            # bf16 rounding of the stored output: 2^-9 relative to the largest element
     assert rel_err(y, yo) < tol, "y"
     off = 0
@@ -1151,7 +1161,7 @@ def test_conv_t3_staged_run_kernel(dev, case):
     yf = y.float()
     assert rel_err(st[..., 0], yf.mean(dim=(1, 2, 3))) < 1e-4 and rel_err(st[..., 1], 1.0 / torch.sqrt(yf.var(dim=(1, 2, 3), unbiased=False) + 1e-3)) < 1e-4
     # the implicit-GEMM kernel computes the same sums in another order: the two kernels agree far below the oracle tolerance
-    y2, st2, gx2, _ = res["mfma"]
+    y2, st2, gx2, _, _ = res["mfma"]
     assert rel_err(y, y2) < 1e-2 and float((y.float() - y2.float()).abs().mean()) < 2e-4 * float(y2.float().abs().mean()) + 1e-6
     for a_, b_ in zip(gxd, gx2):
         assert rel_err(a_, b_) < 1e-2
@@ -1438,6 +1448,7 @@ def test_conv_fuzz_against_oracle(dev, chunk):
         w = rnd((*k, cout, cin) if transposed else (*k, cin, cout), 2000 + i, sc); b = rnd((cout,), 3000 + i)
         if bf:
             xs = [x.bfloat16().float() for x in xs]
+            w = w.bfloat16().float()                          # (the kernels read the weights in the activation type)
         fo = (lambda x, w_, b_: O.conv3d_transpose_same(x, w_, b_, s)) if transposed else (lambda x, w_, b_: O.conv3d_same(x, w_, b_, s))
         yo = fo(torch.cat(xs, -1).double(), w.double(), b.double())
         dy = rnd(tuple(yo.shape), 4000 + i)
@@ -1466,6 +1477,19 @@ def test_conv_fuzz_against_oracle(dev, chunk):
             off += c
         assert rel_err(wd.grad, gw) < (2e-4 if not bf else 2e-4), (tag, "dw", rel_err(wd.grad, gw))      # fp32 accumulation of exact bf16 products
         assert rel_err(bd.grad, gb) < 2e-4, (tag, "db", rel_err(bd.grad, gb))
+        # per element against the sum of |terms| (util.assert_conv_close; the bound is derived in test_convs_at_scale.py).  The values
+        # stay the oracle's, the magnitudes come from the tap-loop reference: the two references cross-check each other here.  A
+        # bf16 forward over several concat members may run as one launch per group of members (util.ref_member_amag).
+        _, mg = ref_conv_with_mag(torch.cat(xs, -1), w, b, s, dy, transposed)
+        am = ref_member_amag(xs, w, b, s, transposed) if bf and len(xs) > 1 else None
+        assert_conv_close(y.cpu(), yo, mg["y"], dtype, tag + " y", amag=am)
+        off = 0
+        for x in xd:
+            c = x.shape[-1]
+            assert_conv_close(x.grad.cpu(), gx[..., off:off + c], mg["dx"][..., off:off + c], dtype, tag + f" dx[{off}]")
+            off += c
+        assert_conv_close(wd.grad.cpu(), gw, mg["dw"], torch.float32, tag + " dW")
+        assert_conv_close(bd.grad.cpu(), gb, mg["db"], torch.float32, tag + " db")
         if st is not None:
             yf = y.detach().float()
             mean = yf.mean(dim=(1, 2, 3)); var = yf.var(dim=(1, 2, 3), unbiased=False)

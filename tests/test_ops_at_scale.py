@@ -29,7 +29,7 @@ import torch
 
 from oracle import m1_oracle as O
 import util
-from util import PKG, ops, assert_close_ew
+from util import PKG, ops, assert_close_ew, assert_conv_close
 
 A_BF, B_BF = 6 * 2.0 ** -9, 1e-3
 A_32, B_32 = 1e-5, 4e-6
@@ -855,27 +855,40 @@ def _run_key(dev, key, seed):
         raise KeyError(op)
 
 
-def _inbwd_case(dev, dtype, dims, c, cout, seed, expect_fused):
-    """y = conv1x1(lrelu(IN(x))) (the pointwise conv3 of an SE block reading the norm2 output): the IN backward from the sums the
+def _inbwd_case(dev, dtype, dims, c, cout, seed, expect_fused, k=(1, 1, 1), kernels=None):
+    """y = conv(lrelu(IN(x))), by default 1x1x1 (the pointwise conv3 of an SE block reading the norm2 output; ``k``: another stride-1
+    kernel, e.g. conv2 reading norm1 -- test_convs_at_scale.py runs the bench step's own layers): the IN backward from the sums the
     conv's data-gradient epilogue emits (ops._INBWD, one partial row per epilogue tile -- thousands at res0) and from the stand-alone
     reduction, both against fp64.  The reference stores the data gradient of the norm's output in the activation type, as the conv
-    does; the weights are given in that type (the conv reads them so)."""
+    does; the weights are given in that type (the conv reads them so).  The activation gradient d(a) the conv hands to the norm is
+    compared per element as well (util.assert_conv_close); ``kernels``: the kernel-log entries the fused data gradient must show."""
     g = _gen(dev, seed)
     shape = (*dims, c)
+    K = c * k[0] * k[1] * k[2]
     x = _as(_randn(shape, g, dev, 1.7) + 0.8 + _ramp(shape, dev) + 0.2 * _randn((1, 1, 1, 1, c), g, dev), dtype)
     gam, bet = 1 + 0.2 * _randn((c,), g, dev), 0.3 + 0.2 * _randn((c,), g, dev)
-    w = _as(_randn((1, 1, 1, c, cout), g, dev, 1.0 / c ** 0.5), dtype)
+    w = _as(_randn((*k, c, cout), g, dev, 1.0 / K ** 0.5), dtype)
     bc = 0.1 * _randn((cout,), g, dev)
     xr, gr, br = (t.double().requires_grad_(True) for t in (x, gam, bet))
     a_ = util.round_grad(util.ref_instnorm_act(xr, gr, br, 0.1), dtype)
-    yr = util.ref_pointwise_conv(a_, w.double(), bc.double())
+    pw = tuple(k) == (1, 1, 1)
+    yr = util.ref_pointwise_conv(a_, w.double(), bc.double()) if pw else util.ref_conv3d_same(a_, w.double(), bc.double(), (1, 1, 1))
     dy = _as(yr.detach().float() + 0.5 * _randn(tuple(yr.shape), g, dev), dtype)   # dy ~ y: da ~ a (W W^T) -- dgamma stays biased
     yr.backward(dy.double())
     with torch.no_grad():
         st = util.ref_in_stats(x.double())
         xhat = (x.double() - st[:, None, None, None, :, 0]) * st[:, None, None, None, :, 1]
         z = xhat * gam.double() + bet.double()
-        da = torch.einsum("ndhwo,co->ndhwc", dy.double(), w.double().reshape(c, cout)).to(dtype).double()
+        if pw:
+            da64 = torch.einsum("ndhwo,co->ndhwc", dy.double(), w.double().reshape(c, cout))
+            mda = torch.einsum("ndhwo,co->ndhwc", dy.double().abs(), w.double().abs().reshape(c, cout))
+    if not pw:
+        # (the input of the conv rounded to the storage type, as the kernel reads it: da does not depend on it, the shapes do)
+        rf, mg_ = util.ref_conv_with_mag(torch.zeros_like(x), w, None, (1, 1, 1), dy)
+        da64, mda = rf["dx"], mg_["dx"]
+        del rf, mg_
+    with torch.no_grad():
+        da = da64.to(dtype).double()
         dz = da * torch.where(z >= 0, 1.0, 0.1)
         mg, mb = (dz * xhat).abs().sum(dim=(0, 1, 2, 3)), dz.abs().sum(dim=(0, 1, 2, 3))
         # the LeakyReLU's branch at z within fp32 error of 0 is a tie (both branches right): left out of dx.  The conv stores the
@@ -890,8 +903,16 @@ def _inbwd_case(dev, dtype, dims, c, cout, seed, expect_fused):
             xd = x.to(dtype).clone().requires_grad_(True)                 # (a fresh leaf per run: x.to(fp32) would be x itself)
             ps = [t.clone().requires_grad_(True) for t in (gam, bet, w, bc)]
             a = ops.instnorm_act(xd, ps[0], ps[1], 0.1, ops.instnorm_stats(xd))
-            y = ops.conv3d_same([a], ps[2], ps[3], (1, 1, 1), (1, 1, 1))
-            y.backward(dy.to(dtype))
+            y = ops.conv3d_same([a], ps[2], ps[3], k, (1, 1, 1))
+            seen = []
+            a.register_hook(lambda g_: seen.append(g_.detach().clone()))
+            with ops.kernel_log() as kl:
+                y.backward(dy.to(dtype))
+                torch.cuda.synchronize()
+            assert len(seen) == 1
+            assert_conv_close(seen[0], da64, mda, dtype, f"d(a) of the conv, fused={on} {(*dims, c)}->{cout} k={k}")
+            if on and kernels is not None:
+                assert [n for n in kl.names if not n.startswith("wgrad")] == list(kernels), (kl.names, kernels)
             return xd.grad, ps[0].grad, ps[1].grad
         finally:
             ops._INBWD["on"] = was

@@ -338,3 +338,114 @@ def assert_close_ew(got: torch.Tensor, ref: torch.Tensor, a: float, b: float, ma
         raise AssertionError(f"{what}: {nbad} of {got.numel()} elements outside |d| <= {a:.3g}*|ref| + {b:.3g}*rms; worst at {idx}: "
                              f"got {float(got.reshape(-1)[k]):.9g} ref {float(r.reshape(-1)[k]):.9g} bound {float(bound.reshape(-1)[k]):.3g} "
                              f"(rms(ref) {rms:.3g})")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# fp64 references of the convolutions, device-agnostic and readable: a loop over the kernel's taps, each tap a shifted (and strided)
+# slice of the input times a (Cin, Cout) matrix.  No library convolution.  Gradients come from autograd.  Called with |x|, |w|, |b|
+# (and |dy| as the upstream gradient) the same code yields the sum of |terms| behind every output, data-gradient and weight-gradient
+# element (ref_conv_with_mag).  tests/test_convs_at_scale.py pins both to oracle/m1_oracle.py.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def same_pads(n: int, k: int, s: int):
+    """(out, before, after) of TensorFlow's SAME padding: total = max((ceil(n/s) - 1)*s + k - n, 0), the smaller half in front."""
+    out = -(-n // s)
+    total = max((out - 1) * s + k - n, 0)
+    return out, total // 2, total - total // 2
+
+
+def ref_conv3d_same(x, w, b, s):
+    """Conv3D(padding='same') on NDHWC in fp64; w (kd, kh, kw, Cin, Cout), b (Cout,) or None, s = (sd, sh, sw)."""
+    x, w = x.double(), w.double()
+    kd, kh, kw, cin, cout = w.shape
+    assert x.shape[-1] == cin, (tuple(x.shape), tuple(w.shape))
+    (od, db, da), (oh, hb, ha), (ow, wb, wa) = (same_pads(int(n), int(k), int(st)) for n, k, st in zip(x.shape[1:4], (kd, kh, kw), s))
+    xp = torch.nn.functional.pad(x, (0, 0, wb, wa, hb, ha, db, da))
+    y = None
+    for a in range(kd):
+        for b_ in range(kh):
+            for c in range(kw):
+                xs = xp[:, a:a + (od - 1) * s[0] + 1:s[0], b_:b_ + (oh - 1) * s[1] + 1:s[1], c:c + (ow - 1) * s[2] + 1:s[2]]
+                t = torch.matmul(xs, w[a, b_, c])
+                y = t if y is None else y + t
+    return y if b is None else y + b.double()
+
+
+def ref_conv3d_transpose_same(x, w, b, s):
+    """Conv3DTranspose(padding='same') on NDHWC in fp64; w (kd, kh, kw, Cout, Cin); out = in * s per axis:
+    out[j, co] = sum over (i, tap) with j = i*s + tap - pb of x[i, :] . w[tap, co, :] + b[co], pb = max(k - s, 0) // 2."""
+    x, w = x.double(), w.double()
+    kd, kh, kw, cout, cin = w.shape
+    assert x.shape[-1] == cin, (tuple(x.shape), tuple(w.shape))
+    n = [int(v) for v in x.shape[1:4]]
+    pb = [max(k - st, 0) // 2 for k, st in zip((kd, kh, kw), s)]
+    full = [max((m - 1) * st + k, p + m * st) for m, st, k, p in zip(n, s, (kd, kh, kw), pb)]
+    y = x.new_zeros((x.shape[0], *full, cout))
+    for a in range(kd):
+        for b_ in range(kh):
+            for c in range(kw):
+                t = torch.matmul(x, w[a, b_, c].transpose(0, 1))
+                y[:, a:a + (n[0] - 1) * s[0] + 1:s[0], b_:b_ + (n[1] - 1) * s[1] + 1:s[1], c:c + (n[2] - 1) * s[2] + 1:s[2]] += t
+    y = y[:, pb[0]:pb[0] + n[0] * s[0], pb[1]:pb[1] + n[1] * s[1], pb[2]:pb[2] + n[2] * s[2]]
+    return y if b is None else y + b.double()
+
+
+def ref_conv_with_mag(x, w, b, s, dy=None, transposed=False):
+    """(ref, mag): dicts with 'y' and, when ``dy`` is given, 'dx', 'dw', 'db' (None without a bias).  ``ref`` is the fp64 convolution and
+    its autograd gradients; ``mag`` is the same computation on |x|, |w|, |b| with |dy| upstream: the sum of |terms| behind every
+    element (for y the bias is one term; every db element sums the |dy| of its channel)."""
+    fn = ref_conv3d_transpose_same if transposed else ref_conv3d_same
+    out = []
+    for f in ((lambda t: t), torch.abs):
+        ins = [f(x.detach().double()).requires_grad_(dy is not None), f(w.detach().double()).requires_grad_(dy is not None),
+               None if b is None else f(b.detach().double()).requires_grad_(dy is not None)]
+        y = fn(ins[0], ins[1], ins[2], s)
+        r = {"y": y.detach()}
+        if dy is not None:
+            y.backward(f(dy.detach().double()))
+            r.update(dx=ins[0].grad, dw=ins[1].grad, db=None if b is None else ins[2].grad)
+        del y
+        out.append(r)
+    return out[0], out[1]
+
+
+def ref_member_amag(xs, w, b, s, transposed=False):
+    """Magnitudes of the values a forward stores in its output when it runs as several launches over groups of concat members, each
+    launch rounding its own contribution and the new running sum to the storage type: sum_m |C_m| + sum_{j < last} |P_j| + 2|b|, with C_m
+    the contribution of member m, P_j the member-prefix sums (every running sum of launches over runs of whole members is one of them)
+    and the bias counted as part of a contribution and of a running sum, whichever launch adds it."""
+    fn = ref_conv3d_transpose_same if transposed else ref_conv3d_same
+    amag, run, off = None, None, 0
+    for j, x_ in enumerate(xs):
+        c = int(x_.shape[-1])
+        cm = fn(x_, w[..., off:off + c] if transposed else w[..., off:off + c, :], None, s)
+        off += c
+        run = cm + (0.0 if b is None else b.double()) if run is None else run + cm
+        amag = cm.abs() if amag is None else amag + cm.abs()
+        if j < len(xs) - 1:
+            amag = amag + run.abs()
+    return amag if b is None else amag + 2 * b.double().abs()
+
+
+# rounding of a stored conv result (a) and fp32 accumulation of exact products, relative to the sum of |terms| (r): derived in the
+# docstring of tests/test_convs_at_scale.py
+CONV_A = {torch.bfloat16: 2.0 ** -8, torch.float32: 4 * 2.0 ** -24}
+CONV_R = 1e-5
+
+
+def assert_conv_close(got, ref, mag, dtype, what, acc=False, r=CONV_R, amag=None):
+    """Per element |got - ref| <= a*|ref| + r*mag, no element left out.  ``dtype``: the type the result is STORED in (fp32 for weight
+    and bias gradients); ``acc``: the kernel added into a slot of that type that already held a value (two roundings); ``mag``: the
+    sum of |terms| behind each element (ref_conv_with_mag, plus |slot| where the kernel accumulates).  ``amag``: the magnitudes of further
+    values that were stored in ``dtype`` on the way (the running sum a multi-launch forward keeps in its output): a*(|ref| + amag)."""
+    got, ref, mag = got.detach(), ref.detach().double(), mag.detach().double()
+    assert got.shape == ref.shape == mag.shape, (what, tuple(got.shape), tuple(ref.shape), tuple(mag.shape))
+    a = CONV_A[dtype] * (2 if acc else 1)
+    bound = a * (ref.abs() if amag is None else ref.abs() + amag.detach().double()) + r * mag
+    excess = (got.double() - ref).abs() - bound
+    k = int(torch.argmax(torch.nan_to_num(excess, nan=float("inf"))))
+    if not (float(excess.reshape(-1)[k]) <= 0.0 and bool(torch.isfinite(got).all())):
+        idx = tuple(int(i) for i in np.unravel_index(k, tuple(got.shape)))
+        nbad = int((excess > 0).sum()) + int((~torch.isfinite(got)).sum())
+        raise AssertionError(f"{what}: {nbad} of {got.numel()} elements outside |d| <= {a:.3g}*|ref| + {r:.3g}*sum|terms|; worst at {idx}: "
+                             f"got {float(got.reshape(-1)[k]):.9g} ref {float(ref.reshape(-1)[k]):.9g} "
+                             f"sum|terms| {float(mag.reshape(-1)[k]):.6g} bound {float(bound.reshape(-1)[k]):.3g}")
