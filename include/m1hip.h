@@ -342,6 +342,72 @@ int m1_dice_bd_fwd(const float* probs, const void* y_true, int y_dtype, const fl
 int m1_dice_bd_bwd(const float* probs, const void* y_true, int y_dtype, const float* phi, long long NV, int nheads, int nc,
                    float w0, float w1, float smooth, const float* ws, const float* dloss, float* dprobs, void* stream);
 
+/* ---- Train-time augmentations : tf2.5/scripts/model/augmentations.py (A:) 36-326, augment_tensors and its helpers ----
+ * x (N,D,H,W,C) fp32 image whose first nimg channels are MRI sequences (3 lesion / 1 zonal; the rest are the label channels of a
+ * probabilistic input), y (N,D,H,W,nc) fp32 label or NULL.  Every op is 2-D over (H,W) with one set of parameters per sample.
+ * Everything random reaches the resampling / intensity kernels through ONE plain-data record per sample, m1_aug_params_t: filled
+ * on the device by m1_aug_draw, or by the caller (tests inject tables).  The kernels never call cos / sin: the six coefficients of
+ * the rotation's projective transform (tfa.image.rotate: [cos, -sin, x_off, sin, cos, y_off], output -> input, about the centre of
+ * the SYMMETRIC-padded slice) are table entries.  Sampling coordinates are fp32 in a fixed operation order without contraction:
+ * (i + 0.5f) * ((float)in / (float)out) - 0.5f for tf.image.resize (TF2 half-pixel centres, no antialias),
+ * floor((i + 0.5f) * ((float)in / (float)out)) for the TF2 nearest resize, (t0 * x + t1 * y) + t2 for the rotation.
+ * `stages`: the M1_AUG_* bits of the stages the hyper-parameters enable (a table bit outside it is ignored); M1_AUG_ZOOM,
+ * M1_AUG_ROTATE or M1_AUG_POOR on a non-square slice -> M1_ERR_UNSUPPORTED (A:60-61,143-148 and A:267-268 use shape[1] for both
+ * axes; A:233-234 crops both axes by the fraction of the first).  dtype: M1_F32 only (M1_BF16 -> M1_ERR_UNSUPPORTED, anything else
+ * M1_ERR_BAD_ARG).  C, nc <= 8, nimg <= min(C, 4).  Out-of-range table entries cannot fault: every source index is clamped.
+ * Results are bit-identical run to run (fp64 per-block partials folded in a fixed order, no atomics); every launch goes to
+ * `stream`, nothing synchronises, nothing is a memset / memcpy node. */
+enum m1_aug_stage {
+    M1_AUG_MASTER = 1, M1_AUG_ZOOM = 2, M1_AUG_FLIP = 4, M1_AUG_ROTATE = 8, M1_AUG_TRANSLATE = 16, M1_AUG_CSHIFT = 32,
+    M1_AUG_GAMMA = 64, M1_AUG_POOR = 128, M1_AUG_NOISE = 256
+};
+typedef struct {
+    uint32_t fired;        /* M1_AUG_* bits: the master coin (A:51) and the stage coins (A:59,66,71,77,88,98,104,109) that came up */
+    uint32_t gamma_ch;     /* bit c: the per-channel coin of A:299 for image channel c */
+    uint32_t poor_ch;      /* bit c: the per-channel coin of A:265 */
+    int32_t scale;         /* A:60-61: side of the resized slice, in [H, ceil(H * zoom_factor)) */
+    int32_t rot_pad;       /* A:223: ceil((diagonal - min(H, W)) / 2), also the start of the central crop (A:233-234) */
+    float rot[6];          /* t0..t5: source x = (t0 * X + t1 * Y) + t2, source y = (t3 * X + t4 * Y) + t5, in the padded slice */
+    int32_t tr[4];         /* A:78-81: pad_top, pad_bottom, pad_right, pad_left */
+    int32_t cs[4];         /* A:89-92: the same for the channel shift */
+    int32_t cs_channel;    /* A:189 */
+    float gamma;           /* A:99 */
+    float noise_std;       /* A:110 */
+    float angle_deg;       /* A:72, informational: the kernels read rot[] */
+    int32_t _pad;
+} m1_aug_params_t;
+/* One thread per sample fills table[n] in the draw order of A:51-111 (a stage that is disabled, or whose coin the master coin
+ * precedes and did not fire, draws nothing).  Draw k of sample n: Philox4x32-10(seed = rng[0] + stream_id * golden,
+ * counter = (rng[1] << 36) + n * 64 + k), rng = a device-resident {seed, step} pair (m1_step_advance moves it).  Uniform floats
+ * are (word >> 9) * 2^-23 (23 bits, as TensorFlow's: lo + u * (hi - lo) then stays below hi), integers in [lo, hi) are
+ * lo + word % (hi - lo).  Hyper-parameters as in A:39-48, as doubles (what Python hands to TF: the integer bounds are
+ * ceil((float)(H * factor)), A:61,78-81,89-92); lesion != 0 for train_obj == 'lesion'.  An empty or oversized integer interval
+ * (ceil(H * zoom_factor) <= H, a pad bound < 1 or > H) is M1_ERR_BAD_ARG; zoom, rotation or poor scan enabled on a non-square
+ * slice M1_ERR_UNSUPPORTED. */
+int m1_aug_draw(m1_aug_params_t* table, int N, const uint64_t* rng, uint64_t stream_id, double prob, double tx_prob,
+                double translate_factor, double rotation_degree, int axial_hflip, double zoom_factor, double gauss_noise_stddev,
+                double chan_shift_factor, int sim_poor_scan, double gamma_lo, double gamma_hi, int H, int W, int nimg, int lesion,
+                void* stream);
+/* ws of every call below: m1_aug_ws_bytes bytes, 8-byte aligned, the same buffer through the three calls of one batch. */
+size_t m1_aug_ws_bytes(int N, int D, int H, int W, int nimg);
+/* zoom -> flip -> rotate -> translate -> channel shift of x into gx and zoom -> flip -> rotate -> translate of y into gy (same
+ * coins and parameters, A:114-120), ONE gather launch evaluated from the output voxel back to the source (at most 16 source reads
+ * per element; the stages' fp32 results are formed one after the other exactly as if each stage had been materialised).  A sample
+ * whose master coin did not fire is copied.  With M1_AUG_GAMMA in `stages` the launch also leaves min / max / sum / sum of squares
+ * of every image channel of gx in ws (per-block fp64 partials + one fold launch). */
+int m1_aug_geom(const float* x, const float* y, const m1_aug_params_t* table, float* gx, float* gy, int N, int D, int H, int W,
+                int C, int nimg, int nc, int stages, int dtype, void* ws, void* stream);
+/* A:306-307: mean and population std of the gamma-powered channels of gx (after m1_aug_geom with M1_AUG_GAMMA). */
+int m1_aug_gamma_stats(const float* gx, const m1_aug_params_t* table, int N, int D, int H, int W, int C, int nimg, int stages,
+                       int dtype, void* ws, void* stream);
+/* gamma curve + re-standardisation (A:298-310), poor scan (A:264-271: the nearest pick of a bilinear tap of the gamma-corrected
+ * volume, four reads) and additive noise (A:314-326) in one pass, one write of `out`.  Noise of voxel v: Box-Muller of
+ * Philox4x32-10(seed = rng[0] + stream_id * golden, counter = (rng[1] << 36) + v), up to four draws per voxel, one per image
+ * channel; rng may be NULL when M1_AUG_NOISE is not in `stages`.  N*D*H*W >= 2^36 voxels: M1_ERR_UNSUPPORTED (the step sits above
+ * bit 36 of the counter). */
+int m1_aug_intensity(const float* gx, const m1_aug_params_t* table, const uint64_t* rng, uint64_t stream_id, float* out, int N,
+                     int D, int H, int W, int C, int nimg, int stages, int dtype, void* ws, void* stream);
+
 /* ---- MonteCarloDropout / Dropout : B:142-143 ; N:462-463 (Philox4x32-10, mask regenerated in bwd) ---- */
 int m1_dropout(const void* x, void* y, long long n, float rate, const uint64_t* rng, uint64_t layer_id, int dtype,
                void* stream);

@@ -15,5 +15,6 @@ from . import losses         # noqa: F401
 from . import optim          # noqa: F401
 from . import unets          # noqa: F401
 from . import ddp            # noqa: F401
+from . import augmentations  # noqa: F401
 
-__all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp"]
+__all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp", "augmentations"]

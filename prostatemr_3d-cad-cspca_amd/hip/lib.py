@@ -52,12 +52,25 @@ class SeGateJob(C.Structure):
         + [("F", C.c_int), ("Fr", C.c_int), ("accumulate", C.c_int), ("_pad", C.c_int)]
 
 
+class m1_aug_params_t(C.Structure):
+    """One sample's augmentation record (include/m1hip.h); ``AUG_DTYPE`` is the same layout for numpy."""
+    _fields_ = [("fired", C.c_uint32), ("gamma_ch", C.c_uint32), ("poor_ch", C.c_uint32), ("scale", C.c_int32),
+                ("rot_pad", C.c_int32), ("rot", C.c_float * 6), ("tr", C.c_int32 * 4), ("cs", C.c_int32 * 4),
+                ("cs_channel", C.c_int32), ("gamma", C.c_float), ("noise_std", C.c_float), ("angle_deg", C.c_float),
+                ("_pad", C.c_int32)]
+
+
+# enum m1_aug_stage
+M1_AUG_MASTER, M1_AUG_ZOOM, M1_AUG_FLIP, M1_AUG_ROTATE, M1_AUG_TRANSLATE = 1, 2, 4, 8, 16
+M1_AUG_CSHIFT, M1_AUG_GAMMA, M1_AUG_POOR, M1_AUG_NOISE = 32, 64, 128, 256
+
+
 class m1_prof_rec_t(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double), ("launches", C.c_longlong)]
 
 
-_vp, _i, _ll, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_uint64, C.c_size_t
+_vp, _i, _ll, _f, _u64, _sz, _d = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_uint64, C.c_size_t, C.c_double
 _desc_p = C.POINTER(m1_conv_desc_t)
 
 # name -> (restype, argtypes).  Must list EVERY symbol include/m1hip.h declares (tests check this).
@@ -121,6 +134,11 @@ SIGNATURES = {
     "m1_dice_bd_ws_floats": (_sz, [_ll, _i]),
     "m1_dice_bd_fwd": (_i, [_vp, _vp, _i, _vp, _ll, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "m1_dice_bd_bwd": (_i, [_vp, _vp, _i, _vp, _ll, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "m1_aug_draw": (_i, [_vp, _i, _vp, _u64, _d, _d, _d, _d, _i, _d, _d, _d, _i, _d, _d, _i, _i, _i, _i, _vp]),
+    "m1_aug_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "m1_aug_geom": (_i, [_vp] * 5 + [_i] * 9 + [_vp, _vp]),
+    "m1_aug_gamma_stats": (_i, [_vp, _vp] + [_i] * 8 + [_vp, _vp]),
+    "m1_aug_intensity": (_i, [_vp, _vp, _vp, _u64, _vp] + [_i] * 8 + [_vp, _vp]),
     "m1_dropout": (_i, [_vp, _vp, _ll, _f, _vp, _u64, _i, _vp]),
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),

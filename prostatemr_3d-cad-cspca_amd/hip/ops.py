@@ -1574,6 +1574,63 @@ def dice_boundary_loss(y_true: torch.Tensor, y_pred: torch.Tensor, weights: Sequ
 
 
 # ---------------------------------------------------------------------------------------------------------
+# train-time augmentations (augment.hip; augmentations.py is the public surface)
+# ---------------------------------------------------------------------------------------------------------
+AUG_RECORD_BYTES = C.sizeof(L.m1_aug_params_t)
+
+
+def _aug_table(table: torch.Tensor, N: int) -> torch.Tensor:
+    _req(table)
+    if table.dtype != torch.uint8 or table.numel() != N * AUG_RECORD_BYTES:
+        raise RuntimeError(f"augmentation table: expected {N} records of {AUG_RECORD_BYTES} bytes (uint8), got {tuple(table.shape)} {table.dtype}")
+    return table
+
+
+def aug_draw(N: int, rng: torch.Tensor, stream_id: int, hyper: Sequence, H: int, W: int, nimg: int, lesion: bool) -> torch.Tensor:
+    """m1_aug_draw: the (N, record bytes) uint8 table of one batch, drawn on the device from the {seed, step} pair ``rng``.
+    ``hyper``: prob, tx_prob, translate_factor, rotation_degree, axial_hflip, zoom_factor, gauss_noise_stddev, chan_shift_factor,
+    sim_poor_scan, gamma_lo, gamma_hi (A:39-48)."""
+    _req(rng)
+    p, tx, tr, rot, flip, zoom, noise, cs, poor, g0, g1 = hyper
+    table = torch.empty((int(N), AUG_RECORD_BYTES), dtype=torch.uint8, device=rng.device)
+    flip = int(flip == True)                                     # noqa: E712 -- `axial_hflip==True` (A:65), the rule of augmentations.enabled_stages
+    L.check(L.load().m1_aug_draw(_p(table), int(N), _p(rng), int(stream_id), float(p), float(tx), float(tr), float(rot), flip,
+                                 float(zoom), float(noise), float(cs), int(bool(poor)), float(g0), float(g1), int(H), int(W), int(nimg),
+                                 int(bool(lesion)), _stream()), "m1_aug_draw")
+    return table
+
+
+def aug_apply(x: torch.Tensor, y: Optional[torch.Tensor], table: torch.Tensor, stages: int, nimg: int,
+              rng: Optional[torch.Tensor] = None, stream_id: int = 0):
+    """The whole chain of A:36-132 on a batch: m1_aug_geom (+ m1_aug_gamma_stats + m1_aug_intensity when an intensity stage is
+    enabled in ``stages``).  x (N,D,H,W,C) fp32, y (N,D,H,W,nc) fp32 or None; returns (image, label)."""
+    _req(x, y, rng)
+    if x.dim() != 5 or (y is not None and (y.dim() != 5 or y.shape[:4] != x.shape[:4])):
+        raise RuntimeError("augmentations: image (N,D,H,W,C) and label (N,D,H,W,nc) over the same voxels expected")
+    if x.dtype != torch.float32 or (y is not None and y.dtype != torch.float32):
+        raise RuntimeError("augmentations: fp32 image and label expected (what the generator yields)")
+    N, D, H, W, Cn = (int(v) for v in x.shape)
+    nc = int(y.shape[-1]) if y is not None else 0
+    _aug_table(table, N)
+    lib, st = L.load(), _stream()
+    ws = torch.empty(max(int(lib.m1_aug_ws_bytes(N, D, H, W, int(nimg))), 8) // 8, dtype=torch.float64, device=x.device)
+    gx = torch.empty_like(x)
+    gy = torch.empty_like(y) if y is not None else None
+    dims = (N, D, H, W, Cn, int(nimg))
+    L.check(lib.m1_aug_geom(_p(x), _p(y), _p(table), _p(gx), _p(gy), *dims, nc, int(stages), L.M1_F32, _p(ws), st), "m1_aug_geom")
+    if not stages & (L.M1_AUG_GAMMA | L.M1_AUG_POOR | L.M1_AUG_NOISE):
+        return gx, gy
+    if stages & L.M1_AUG_NOISE and rng is None:
+        raise RuntimeError("augmentations: the noise stage needs a device {seed, step} pair (rng=)")
+    if stages & L.M1_AUG_GAMMA:
+        L.check(lib.m1_aug_gamma_stats(_p(gx), _p(table), *dims, int(stages), L.M1_F32, _p(ws), st), "m1_aug_gamma_stats")
+    out = torch.empty_like(x)
+    L.check(lib.m1_aug_intensity(_p(gx), _p(table), _p(rng), int(stream_id), _p(out), *dims, int(stages), L.M1_F32, _p(ws), st),
+            "m1_aug_intensity")
+    return out, gy
+
+
+# ---------------------------------------------------------------------------------------------------------
 # dropout (standalone), cast
 # ---------------------------------------------------------------------------------------------------------
 class _Dropout(torch.autograd.Function):

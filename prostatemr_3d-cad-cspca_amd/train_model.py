@@ -9,8 +9,12 @@ What differs from the reference, and why (its harness bugs a
   * data: the reference reads ``.npy`` paths from ``.xlsx`` sheets (data_generators.py:30-90; needs pandas+openpyxl+cv2 and
     data that is not shipped).  Here ``--TRAIN_NPY_DIR`` takes a directory of ``image_*.npy`` / ``label_*.npy`` pairs, and
     without it ``--SYNTHETIC_SAMPLES`` whitened-noise volumes with a ball lesion are generated (same I/O contract:
-    ``({"image": x}, {"detection": y[, "KL": 0]})``, data_generators.py:79-88).  Augmentation (model/augmentations.py) is
-    the reference's CPU input pipeline and out of scope.
+    ``({"image": x}, {"detection": y[, "KL": 0]})``, data_generators.py:79-88).
+  * augmentation: the reference maps ``augment_tensors`` over every sample on the CPU (T:180).  Here ``--AUGMENT 1`` (a flag of
+    this build, default 0) sends every batch through ``augmentations.augment_tensors`` on the GPU with ``--AUGM_PARAMS`` and
+    ``--TRAIN_OBJ`` before ``fit`` sees it, every sample with its own draws from a {seed, step} pair of the trainer's own (seeded
+    from ``--SEED``; the model's dropout stream is not touched; each rank augments its shard under its own stream id).
+    ``--AUGM_PARAMS`` on the command line is a flat list: eleven numbers, the last two being the gamma range.
   * multi-GPU: one process per GPU under torchrun + RCCL all-reduce (ddp.py) instead of ``--GPU_DEVICE_IDs`` +
     tf.distribute.MirroredStrategy inside one process (T:167-170); the flag is accepted and must agree with WORLD_SIZE.
   * ``--LR_MODE CLR`` refers to a CyclicLR the reference never imports (T:247-251): not offered.  ``--OPTIMIZER momentum``
@@ -32,7 +36,8 @@ import numpy as np
 import torch
 
 from . import callbacks as cbs
-from . import ddp, initializers, losses, optim, unets
+from . import augmentations, ddp, initializers, losses, optim, unets
+from .hip import ops
 
 
 def _triples(v: Sequence, n: int) -> Tuple[Tuple[int, int, int], ...]:
@@ -45,6 +50,17 @@ def _triples(v: Sequence, n: int) -> Tuple[Tuple[int, int, int], ...]:
         out = tuple(tuple(int(a) for a in v[3 * i:3 * i + 3]) for i in range(n))
     assert len(out) == n
     return out
+
+
+class _AugmParams(argparse.Action):
+    """``--AUGM_PARAMS`` typed on a command line: eleven numbers, the ten entries of augmentations.py:39-48 with the gamma range
+    (the nested ``[0.50, 1.50]`` of the default, which cannot be typed) as the last two."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if len(values) != 11:
+            parser.error(f"--AUGM_PARAMS takes 11 numbers (prob tx_prob translate rotation hflip zoom noise chan_shift poor_scan "
+                         f"gamma_lo gamma_hi), got {len(values)}")
+        setattr(namespace, self.dest, list(values))
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -97,7 +113,8 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--FOCAL_LOSS_GAMMA', type=float, default=2.0)
     prsr.add_argument('--DSC_BD_LOSS_WEIGHTS', type=float, default=[0.50, 0.50], nargs='+')
     prsr.add_argument('--ELBO_LOSS_PARAMS', type=float, default=[10], nargs='+')
-    prsr.add_argument('--AUGM_PARAMS', type=float, default=[1.00, 0.25, 0.15, 10.0, True, 1.20, 0.10, 0.025, True, [0.50, 1.50]], nargs='+')
+    prsr.add_argument('--AUGM_PARAMS', type=float, default=[1.00, 0.25, 0.15, 10.0, True, 1.20, 0.10, 0.025, True, [0.50, 1.50]], nargs='+', action=_AugmParams)
+    prsr.add_argument('--AUGMENT', type=int, default=0, help="1: train-time augmentations on the GPU (augmentations.augment_tensors with --AUGM_PARAMS)")
     # This build's data source (the reference's .xlsx sheets point at data that is not shipped)
     prsr.add_argument('--TRAIN_NPY_DIR', type=str, default=None, help="directory of image_*.npy (D,H,W,C) / label_*.npy (D,H,W) pairs")
     prsr.add_argument('--SYNTHETIC_SAMPLES', type=int, default=8, help="training samples per fold when no .npy directory is given")
@@ -158,6 +175,16 @@ def batches(gen: Iterator, batch_size: int, device, rank: int = 0, world: int = 
         xs, ys = zip(*[next(gen) for _ in range(batch_size)])
         bx = {k: torch.from_numpy(np.stack([x[k] for x in xs])[mine.start:mine.stop]).to(device) for k in xs[0]}
         by = {k: torch.from_numpy(np.stack([y[k] for y in ys])[mine.start:mine.stop]).float().to(device) for k in ys[0]}
+        yield bx, by
+
+
+def augmented(gen: Iterator, augm_params: Sequence, train_obj: str, seed: int, device, rank: int = 0) -> Iterator:
+    """``dataset.map(augment_tensors)`` (T:180) behind ``batches``: every batch goes through the GPU chain, every sample with its
+    own draws, keyed by a device {seed, step} pair of this generator's own that advances once per batch."""
+    rng = augmentations.new_rng(seed, device)
+    for bx, by in gen:
+        bx, by = augmentations.augment_tensors(bx, by, augm_params, train_obj=train_obj, rng=rng, stream_id=rank)
+        ops.step_advance(None, rng)
         yield bx, by
 
 
@@ -228,6 +255,9 @@ def train_fold(args, f: int, device, rank: int = 0, world: int = 1):
         'Batch size (%d) should be a multiple of the number of GPUs (%d).' % (args.BATCH_SIZE, world)          # T:170
 
     train_gen = batches(custom_data_generator(cases, probabilistic=prob, mode='train'), args.BATCH_SIZE, device, rank, world)
+    if args.AUGMENT:                                                            # T:180 (off: the generator's batches, untouched)
+        train_gen = augmented(train_gen, augmentations.parse_augm_params(args.AUGM_PARAMS), args.TRAIN_OBJ,
+                              args.SEED + 7919 + 1000 * f, device, rank)
 
     # U-Net definition (T:189-207)
     unets.network_blocks.set_init_seed(args.SEED)
