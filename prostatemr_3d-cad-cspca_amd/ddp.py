@@ -12,7 +12,7 @@ are complete at a known point of the backward pass: per core ``a`` = decoder + l
 gates + bottleneck block, ``c`` = encoder (M1Net.exchange_groups).  The model marks the autograd nodes that close a group
 (``M1Core.forward`` -> ``GradReducer.mark``); when the last marked node of a group has run in every core pass of the
 step, the group's range is all-reduced **from a communication stream** that waits for exactly the kernels enqueued so
-far (main stream + the side streams of ops.branch), while the backward of the remaining layers keeps the main stream
+far (main stream + the side streams of ops.branch, hip/streams.py), while the backward of the remaining layers keeps the main stream
 busy.  ``finish()`` sends whatever is left (groups whose marks never fired, then the small bias/norm/SE tail) and makes
 the main stream wait for the communication stream before the optimiser kernel reads the buffer.  Inside a hipGraph
 capture the same calls become graph edges, so the whole step -- RCCL kernels included -- replays as one graph.
@@ -97,7 +97,7 @@ class GradReducer:
              on_origin: Optional[Callable[[], bool]] = None) -> None:
         """``ranges[key]`` = [lo, hi) of group ``key`` inside ``flat_grad``; ``order`` = the order groups are expected to
         complete in; ``tail`` = the range exchanged last (biases, norms, SE); ``side_streams()`` = the streams that may
-        hold backward kernels of the step, the stream the step started on first (ops.exchange_streams)."""
+        hold backward kernels of the step, the stream the step started on first (hip/streams.py exchange_streams)."""
         self.flat, self.ranges, self.order, self.tail = flat_grad, dict(ranges), list(order), tuple(tail)
         if side_streams is not None:
             self._side_streams = side_streams

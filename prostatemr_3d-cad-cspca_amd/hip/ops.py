@@ -8,12 +8,17 @@ from __future__ import annotations
 
 import ctypes as C
 import os as _os
-import weakref
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
+from .debug import trace_reset, trace_snapshot          # noqa: F401 -- first: installs the M1_DEBUG_* patches (torch.empty, lib.check)
 from . import lib as L
+from .streams import (_BRANCH, _FOLD, _WGP, _p, _req, _run_deferred_wgrads, _stream, branch, exchange_streams,  # noqa: F401
+                      finish_queued_for_exchange, fold_async_default, fold_drop, fold_pending, join_side_streams,
+                      on_origin_stream, submit_wgrad)
+from .gradslot import _GradSlot, _slot_of, _slot_target, _slot_written, batch_tail, fanout          # noqa: F401
+from .panels import _PANEL_EPOCH, _conv_ws, _pair_panel_ws, _panel_ws, invalidate_panels, repack_all     # noqa: F401
 
 IN_EPS = 1e-3
 
@@ -24,110 +29,6 @@ def _dt(t: torch.Tensor) -> int:
     if t.dtype == torch.bfloat16:
         return L.M1_BF16
     raise RuntimeError(f"unsupported activation dtype {t.dtype} (float32 / bfloat16 only)")
-
-
-# ---- debug switches (environment, read once): never on in the product path ---------------------------------------------------
-# M1_DEBUG_POISON=1   every uninitialised allocation starts as NaN bit patterns (0xFF bytes): a kernel reading what no kernel wrote
-#                     shows up as NaN in the results of an ordinary in-order run instead of as a run-dependent value under concurrency
-# M1_DEBUG_POISON=2   additionally a scribble launch (m1_debug_scribble: NaN pattern in every LDS word, VGPR and AGPR of all CUs) in
-#                     front of every entry point: reads of LDS / registers the kernel never wrote become NaN as well
-# M1_DEBUG_TRACE=n    a 64-bit checksum of every tensor an op allocated (outputs, workspaces) into slot i of an n-slot device log,
-#                     launched right behind the entry point that wrote it -- one kernel per tensor, capturable, so two processes can be
-#                     compared op by op inside a REPLAYED graph (trace_reset / trace_snapshot; tools/dbg/first_diff.py)
-_POISON = int(_os.environ.get("M1_DEBUG_POISON", "0") or 0)
-_TRACE = {"n": int(_os.environ.get("M1_DEBUG_TRACE", "0") or 0), "log": None, "names": [], "recent": [], "i": 0}
-if _POISON or _TRACE["n"]:
-    _empty, _empty_like = torch.empty, torch.empty_like
-
-    def _poison(t):
-        if t.is_cuda and t.numel():
-            if _POISON:
-                t.fill_(float("nan") if t.is_floating_point() else (255 if t.dtype == torch.uint8 else -1))
-            if _TRACE["n"]:
-                _TRACE["recent"].append(t)
-        return t
-    torch.empty = lambda *a, **k: _poison(_empty(*a, **k))
-    torch.empty_like = lambda *a, **k: _poison(_empty_like(*a, **k))
-
-if _TRACE["n"]:
-    _check0 = L.check
-
-    def _traced_check(rc, what):
-        _check0(rc, what)
-        rec, _TRACE["recent"] = _TRACE["recent"], []
-        if _TRACE["log"] is None:
-            return
-        lib, st = L.load(), torch.cuda.current_stream().cuda_stream
-        for t in rec:
-            i = _TRACE["i"]
-            nb = t.numel() * t.element_size()
-            if i >= _TRACE["n"] or (t.data_ptr() & 3) or not t.is_contiguous():
-                continue
-            _check0(lib.m1_debug_checksum(t.data_ptr(), nb, _TRACE["log"].data_ptr() + 8 * i, st), "m1_debug_checksum")
-            _TRACE["names"].append((what, tuple(t.shape), str(t.dtype)))
-            _TRACE["i"] = i + 1
-    L.check = _traced_check
-
-
-def trace_reset(device=None) -> None:
-    """M1_DEBUG_TRACE: start a step's log (slot 0 next; the device log is zeroed by a fill on the current stream)."""
-    if not _TRACE["n"]:
-        return
-    if _TRACE["log"] is None:
-        _TRACE["log"] = torch.zeros(_TRACE["n"], dtype=torch.int64, device=device or torch.device("cuda", torch.cuda.current_device()))
-    _TRACE["names"], _TRACE["recent"], _TRACE["i"] = [], [], 0
-
-
-def trace_snapshot():
-    """M1_DEBUG_TRACE: (names, checksums) of the step the log holds -- after a synchronize."""
-    if not _TRACE["n"] or _TRACE["log"] is None:
-        return None
-    torch.cuda.synchronize()
-    return list(_TRACE["names"]), _TRACE["log"][:_TRACE["i"]].cpu().clone()
-
-
-def _req(*ts):
-    side = None
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("M1 HIP ops need tensors on a GPU (cuda/HIP) device: the HIP extension is the only "
-                               "compute path of this package; there is no CPU fallback")
-        if not t.is_contiguous():
-            raise RuntimeError("M1 HIP ops need contiguous NDHWC tensors")
-        # An op running on a branch stream (ops.branch: SE shortcut, attention gates, the posterior lane) reads tensors that were
-        # allocated on the stream the step started on.  The caching allocator hands a freed block back to its OWN stream at once: the
-        # moment autograd drops such a tensor (its last backward node has been enqueued, not executed) a later allocation of the main
-        # stream could overwrite it under the branch's kernel.  Eager launches rarely lose that race; a replayed hipGraph, whose
-        # branches run with no host pacing, did (round 4: gradients of the deep levels off by 10-40 % in 2 of 5 runs of the captured
-        # probabilistic step).  record_stream ties the block to the branch stream as well (no-op for blocks of that stream).
-        if side is None:
-            side = _side_stream()
-        if side:
-            t.record_stream(side)
-
-
-def _side_stream():
-    """The current stream when it is a branch stream of the running step, else False."""
-    if not _BRANCH["on"]:
-        return False
-    origin = _BRANCH.get("origin")
-    if origin is None:
-        return False
-    cur = torch.cuda.current_stream()
-    return cur if cur != origin else False
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    s = torch.cuda.current_stream().cuda_stream
-    if _POISON >= 2:
-        L.load().m1_debug_scribble(0, 8, s)
-    return s
 
 
 def _ws(N: int, V: int, Cn: int, nsums: int, device) -> torch.Tensor:
@@ -155,7 +56,13 @@ def _desc(srcs: Sequence[torch.Tensor], cout: int, k, s) -> L.m1_conv_desc_t:
     return d
 
 
-def _sink(param: torch.Tensor, like: Optional[torch.Tensor] = None):
+def _nvc(x: torch.Tensor, k: int = 1) -> Tuple[int, int, int]:
+    """(N, V, C) of an NDHWC tensor whose last axis holds ``k`` groups of C channels (k = 2: the {mu, logsigma} of a latent head)."""
+    N, Cn = int(x.shape[0]), int(x.shape[-1]) // k
+    return N, x.numel() // (N * k * Cn), Cn
+
+
+def _sink(param: torch.Tensor):
     """(buffer, accumulate, autograd_return) for a parameter gradient.  A parameter bound to an optimiser's flat
     gradient buffer (optim.FlatParams sets ``_m1_gsink``) gets its gradient ACCUMULATED there by the kernel and
     autograd receives None (no per-parameter tensors, no AccumulateGrad adds, no gather pass)."""
@@ -163,456 +70,21 @@ def _sink(param: torch.Tensor, like: Optional[torch.Tensor] = None):
     if g is not None:
         param._m1_live = True            # (a backward kernel writes this parameter's gradient: optim.FlatParams.live_ranges)
         return g, 1, None
-    t = torch.empty_like(param if like is None else like, dtype=torch.float32)
+    t = torch.empty_like(param, dtype=torch.float32)
     return t, 0, t
 
 
-# ---------------------------------------------------------------------------------------------------------
-# data gradients of tensors with several consumers
-# ---------------------------------------------------------------------------------------------------------
-class _GradSlot:
-    """The one gradient buffer of a tensor that feeds several layers (an SE block's input feeds conv1 and conv4,
-    network_blocks.py:53,64; an encoder output also feeds its attention gate, networks.py:584-590).  The first backward
-    kernel to produce a gradient for the tensor allocates the buffer, the following ones ACCUMULATE into it in their own
-    epilogue (m1_conv3d_dgrad / m1_convT3d_dgrad ``accumulate``, m1_mul_sigma_bwd ``accumulate_dx``): the per-consumer
-    gradient tensors and autograd's add passes over them disappear."""
-    __slots__ = ("buf", "event", "stream", "tail_init")
-
-    def __init__(self):
-        self.buf = None
-        self.event = None      # recorded after the last kernel that wrote ``buf`` (only when branches run on side streams)
-        self.stream = None
-        self.tail_init = False # the region of ``buf`` behind a batch_tail() holds gradient sums already
-
-
-class _TailRef:
-    """Gradient slot of ``x[start:]`` for an ``x`` that has a slot (batch_tail): the reader's backward kernel writes the tail
-    region of x's own gradient buffer."""
-    __slots__ = ("slot", "start", "full_shape")
-
-    def __init__(self, slot, start, full_shape):
-        self.slot, self.start, self.full_shape = slot, int(start), tuple(full_shape)
-
-
-def _slot_of(t: torch.Tensor):
-    ref = getattr(t, "_m1_gslot_tail", None)
-    return ref if ref is not None else getattr(t, "_m1_gslot", None)
-
-
-def _slot_target(slot, like: torch.Tensor):
-    """(gradient tensor, accumulate flag) for a data gradient shaped like ``like``."""
-    if slot is None:
-        return torch.empty_like(like), 0
-    if isinstance(slot, _TailRef):
-        ref, slot = slot, slot.slot
-        b = slot.buf
-        if b is None or tuple(b.shape) != ref.full_shape or b.dtype != like.dtype:
-            if b is not None:
-                return torch.empty_like(like), 0          # (a buffer of another shape owns the slot: plain gradient tensor)
-            b = torch.empty(ref.full_shape, dtype=like.dtype, device=like.device)
-            b[:ref.start].zero_()                         # nobody has written the head of the batch yet
-            slot.buf, slot.tail_init = b, False
-        elif slot.event is not None and slot.stream != torch.cuda.current_stream():
-            torch.cuda.current_stream().wait_event(slot.event)
-            b.record_stream(torch.cuda.current_stream())
-        view = b[ref.start:]
-        if tuple(view.shape) != tuple(like.shape) or not view.is_contiguous():
-            return torch.empty_like(like), 0
-        acc = 1 if slot.tail_init else 0
-        slot.tail_init = True
-        return view, acc
-    b = slot.buf
-    if b is not None and b.shape == like.shape and b.dtype == like.dtype and b.is_contiguous():
-        if slot.event is not None and slot.stream != torch.cuda.current_stream():
-            torch.cuda.current_stream().wait_event(slot.event)     # the previous writer ran on another stream
-            b.record_stream(torch.cuda.current_stream())           # (the buffer belongs to the stream of its first writer, see _req)
-        return b, 1
-    g = torch.empty_like(like)
-    if b is None:
-        slot.buf, slot.tail_init = g, True               # (written whole by this kernel)
-    return g, 0
-
-
-def _slot_written(slot) -> None:
-    """Call after enqueueing the kernel that wrote / accumulated into ``slot.buf`` (orders readers on other streams)."""
-    if isinstance(slot, _TailRef):
-        slot = slot.slot
-    if slot is not None and _BRANCH["on"]:
-        ev = torch.cuda.Event()
-        ev.record()
-        slot.event, slot.stream = ev, torch.cuda.current_stream()
-
-
-# ---------------------------------------------------------------------------------------------------------
-# independent branches on side streams
-# ---------------------------------------------------------------------------------------------------------
-_BRANCH = {"on": _os.environ.get("M1_STREAMS", "1") != "0", "streams": {}, "used": set(), "depth": 0}
-
-
-# Deferred folds of the weight-gradient partial copies (m1_wgrad_defer): with gradients going to the flat buffer nothing reads a
-# weight gradient before join_side_streams, so the ~130 fold launches of a step (5-10 us each, a few dozen blocks, alone on
-# their stream) become a handful of batched ones there.  The workspaces holding the copies are kept until then.
-_FOLD = {"on": _os.environ.get("M1_WG_FOLD_BATCH", "1") != "0", "keep": [],
-         # M1_FOLD_ASYNC = n > 0 (default 24, one batched launch): every n queued weight gradients the folds queued so far run on
-         # a stream of their own NEXT TO the backward pass (bandwidth-bound folds beside MFMA-bound convolutions) instead of
-         # all at its end, where they ran alone on the GPU (0.8 ms of the C3 step)
-         "async": int(_os.environ.get("M1_FOLD_ASYNC", "-1")), "stream": None,
-         "async_mb": int(_os.environ.get("M1_FOLD_ASYNC_MB", "0")), "bytes": 0}
-
-
-# Deferred weight gradients of the deep levels (round 6).  A weight gradient feeds nothing before the optimiser, and the skip test of
-# round 6 showed that the replayed step is the SUM of its kernels -- except for what runs on the fold stream, which rides for free next
-# to the data-gradient chain.  Weight gradients are therefore not launched where autograd calls them: they are queued (operands kept
-# alive) and launched, in call order, on the fold stream with the next batch of folds -- no fork / join per op (weight gradients on
-# streams of their own WITH a fork and a join each were measured slower in rounds 2, 3 and 6).  M1_WG_DEFER_VOX limits this to layers
-# with at most that many input voxels per launch (0 = launch in place, round 5).  Same box, C3: in place 22.76 ms, <= 16,000 voxels
-# 22.6, <= 520,000 22.29, all 22.00 ms (90.9 volumes/s) at a batch interval of 11-13 (M1_FOLD_ASYNC; 8: 23.6, 16: 22.8, 24: 22.8);
-# profiles/r06_ab_deferred_weight_gradients.txt.
-_WGP = {"maxvox": int(_os.environ.get("M1_WG_DEFER_VOX", str(1 << 40)) or 0), "jobs": [], "extra": []}
-
-
-def _run_deferred_wgrads(stream_handle, stream) -> None:
-    """Launch the queued weight gradients (in call order) on ``stream``; the caller has ordered it behind their operands."""
-    jobs, _WGP["jobs"] = _WGP["jobs"], []
-    if not jobs:
-        return
-    lib = L.load()
-    lib.m1_wgrad_defer(1)
-    try:
-        for fn, d, dy, wbuf, bbuf, ws, acc_w, _srcs in jobs:
-            L.check(fn(C.byref(d), _p(dy), _p(wbuf), _p(bbuf), _p(ws), acc_w, stream_handle), "m1_conv3d_wgrad (deferred)")
-    finally:
-        lib.m1_wgrad_defer(0)
-    for t, made_on in _WGP["extra"]:
-        if made_on != stream:
-            t.record_stream(stream)
-    _WGP["extra"] = []
-
-
-def fold_async_default(n: int) -> None:
-    """Model-level default of the M1_FOLD_ASYNC interval (the environment variable wins).  Measured optimum, same box: 10-12 for
-    the hierarchical probabilistic model (~130 weight gradients per step: 26.7 ms against 27.3 at 24, 27.7 without, 27.6-27.9
-    at <= 8), 24 for the deterministic one (~60 per step: 7.87 ms against 8.01 at 12, 7.94 without)."""
-    if "M1_FOLD_ASYNC" not in _os.environ:
-        _FOLD["async"] = int(n)
-
-
-def _fold_async() -> None:
-    """Run the queued folds on the fold stream, ordered behind everything enqueued so far.  Only from the stream the step started
-    on (a fork of a fork breaks graph capture, see ``branch``): weight gradients of branch streams wait for the next trigger."""
-    origin = _BRANCH.get("origin")
-    cur = torch.cuda.current_stream()
-    if origin is None or cur != origin or not _FOLD["keep"]:
-        return
-    fs = _FOLD["stream"]
-    if fs is None:
-        fs = _FOLD["stream"] = torch.cuda.Stream(device=cur.device)
-    fs.wait_stream(cur)                                   # (first: the fold stream joins a capture through its origin)
-    for s in _BRANCH["used"]:
-        if s != cur and s != fs:
-            fs.wait_stream(s)
-    _BRANCH["used"].add(fs)
-    try:
-        with torch.cuda.stream(fs):
-            _run_deferred_wgrads(fs.cuda_stream, fs)
-            L.check(L.load().m1_wgrad_fold_pending(fs.cuda_stream), "m1_wgrad_fold_pending")
-        for ws, made_on in _FOLD["keep"]:
-            if made_on != fs:
-                ws.record_stream(fs)
-    finally:
-        _FOLD["keep"].clear(); _FOLD["bytes"] = 0
-
-
-def fold_pending() -> None:
-    """Run the queued weight-gradient folds on the current stream (which must be ordered behind the weight-gradient kernels)."""
-    if _FOLD["keep"]:
-        try:
-            _run_deferred_wgrads(_stream(), torch.cuda.current_stream())
-            L.check(L.load().m1_wgrad_fold_pending(_stream()), "m1_wgrad_fold_pending")
-            cur = torch.cuda.current_stream()
-            for ws, made_on in _FOLD["keep"]:
-                if made_on != cur:
-                    ws.record_stream(cur)             # read here, allocated on a branch stream
-        finally:
-            _FOLD["keep"].clear(); _FOLD["bytes"] = 0
-
-
-def finish_queued_for_exchange() -> None:
-    """Before a gradient group is exchanged during backward (ddp.GradReducer): the current stream waits for the branch streams
-    (without retiring them) and runs the weight-gradient folds queued so far."""
-    if _FOLD["keep"]:
-        cur = torch.cuda.current_stream()
-        # a hook that fires on a lane (the posterior pass runs its backward on a side stream, networks.py M1_PQ_LANES) must also
-        # wait for the ORIGIN stream: the queue holds the prior's partial copies too, whose weight-gradient kernels are in flight
-        # there (``used`` only lists side streams)
-        origin = _BRANCH.get("origin")
-        if origin is not None and origin != cur:
-            cur.wait_stream(origin)
-        for s in _BRANCH["used"]:
-            if s != cur:
-                cur.wait_stream(s)
-        fold_pending()
-
-
-def on_origin_stream() -> bool:
-    """True unless the current stream is a branch stream of the running step (autograd runs a branch's backward nodes on it)."""
-    origin = _BRANCH.get("origin")
-    return origin is None or not torch.cuda.is_available() or torch.cuda.current_stream() == origin
-
-
-def exchange_streams():
-    """Streams that may hold backward kernels of the running step, the origin stream FIRST (a communication stream must join a
-    graph capture through the stream the capture started on before it takes edges from forked streams), for ddp.GradReducer."""
-    origin = _BRANCH.get("origin")
-    out = [origin] if origin is not None else []
-    return out + [s for s in _BRANCH["used"] if s is not origin]
-
-
-def fold_drop() -> None:
-    _WGP["jobs"], _WGP["extra"] = [], []
-    if _FOLD["keep"]:
-        L.load().m1_wgrad_fold_drop()
-        _FOLD["keep"].clear(); _FOLD["bytes"] = 0
-
-
-def join_side_streams() -> None:
-    """The current stream waits for every side stream used since the last call.  Backward kernels that only add into
-    parameter-gradient sinks return nothing to autograd, so the engine never orders them before the caller: gather_grads /
-    zero_grad do it here (inside a capture this is also what rejoins the forked streams)."""
-    if _BRANCH["used"]:
-        cur = torch.cuda.current_stream()
-        for s in _BRANCH["used"]:
-            if s != cur:
-                cur.wait_stream(s)
-        _BRANCH["used"].clear()
-    fold_pending()
-
-
-class branch:
-    """``with ops.branch(device, k) as br: y = f(x)`` then ``br.join(y)``: runs an independent part of the step (the conv4
-    shortcut of an SE block next to its conv1-conv2-conv3 chain; the attention gates next to the decoder) on side stream
-    ``k``; autograd runs the backward of these ops on the same stream, so both directions overlap, inside a captured graph
-    as well (fork/join become graph dependencies).  Most kernels of the deep levels fill a fraction of the 256 CUs: measured
-    -8 % per C2 train step (SE shortcuts + gates), -4 % on the full probabilistic model.  M1_STREAMS=0 runs everything in order.
-    Tensors handed to the branch must stay referenced until ``join`` (they are read on the side stream)."""
-
-    def __init__(self, device, k: int = 0):
-        # a branch opened INSIDE another branch runs in line on its parent's stream: forks of forks segfault the HIP graph
-        # capture of this ROCm release (and every fork then starts from the capture's origin stream)
-        self.on = _BRANCH["on"] and device.type == "cuda" and _BRANCH["depth"] == 0
-        if self.on:
-            _BRANCH["origin"] = torch.cuda.current_stream(device)          # (depth 0: the stream the step runs on)
-            key = (device, k)
-            if key not in _BRANCH["streams"]:
-                _BRANCH["streams"][key] = torch.cuda.Stream(device=device)
-            self.side = _BRANCH["streams"][key]
-            self.cur = torch.cuda.current_stream(device)
-            self.ctx = torch.cuda.stream(self.side)
-
-    def __enter__(self):
-        if self.on:
-            self.side.wait_stream(self.cur)
-            _BRANCH["used"].add(self.side)
-            self.ctx.__enter__()
-            _BRANCH["depth"] += 1
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            _BRANCH["depth"] -= 1
-            self.ctx.__exit__(*exc)
-        return False
-
-    def join(self, *tensors):
-        """Make the current stream wait for the branch; ``tensors``: its results that the current stream will read."""
-        if self.on:
-            self.cur.wait_stream(self.side)
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(self.cur)
-
-
-class _Fanout(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, k, slot, owner):
-        ctx.slot, ctx.owner = slot, owner
-        ctx.set_materialize_grads(False)
-        return tuple(x.view_as(x) for _ in range(k))
-
-    @staticmethod
-    def backward(ctx, *gs):
-        slot = ctx.slot
-        if isinstance(slot, _TailRef):
-            # aliases of a batch_tail() output: the consumers wrote (and summed) their shares straight into the tail of the parent
-            # tensor's gradient buffer; hand that view on -- _BatchTail.backward recognises it and no slice backward runs
-            ref, slot = slot, slot.slot
-            full = slot.buf
-            buf = None
-            if full is not None and tuple(full.shape) == ref.full_shape and slot.tail_init:
-                if slot.event is not None and slot.stream != torch.cuda.current_stream():
-                    torch.cuda.current_stream().wait_event(slot.event)
-                    full.record_stream(torch.cuda.current_stream())
-                buf = full[ref.start:]
-            rest = None
-            for g in gs:
-                if g is None or (buf is not None and g.data_ptr() == buf.data_ptr() and g.shape == buf.shape):
-                    continue
-                if buf is not None:
-                    buf.add_(g)
-                else:
-                    rest = g if rest is None else rest + g
-            return (buf if buf is not None else rest), None, None, None
-        buf = slot.buf
-        if buf is not None and slot.event is not None and slot.stream != torch.cuda.current_stream():
-            # the last share was added on another stream than this node's (a gate branch, the posterior lane): the readers of the
-            # summed gradient are ordered behind THIS node by autograd, so it must wait for that write itself
-            torch.cuda.current_stream().wait_event(slot.event)
-            buf.record_stream(torch.cuda.current_stream())
-        if ctx.owner:
-            slot.buf, slot.tail_init = None, False
-        rest = None
-        for g in gs:
-            if g is None or (buf is not None and g.data_ptr() == buf.data_ptr() and g.shape == buf.shape):
-                continue                      # nothing, or the slot buffer itself (already holds that consumer's share)
-            if buf is not None:
-                buf.add_(g)                   # a consumer that does not accumulate in its kernel: fold it into the slot
-            else:
-                rest = g if rest is None else rest + g
-        return (buf if buf is not None else rest), None, None, None
-
-
-def fanout(x: torch.Tensor, k: int):
-    """``k`` aliases of ``x``, one per consumer.  Their backward kernels sum the gradient of ``x`` in one shared buffer (see
-    _GradSlot); consumers without an accumulating kernel still work (their gradient is added here).  Each alias must be
-    used by exactly one consumer.  Nested use (a module forks an alias it was handed) shares the outer buffer."""
-    if k <= 1 or not torch.is_grad_enabled() or not x.requires_grad:
-        return (x,) * k
-    tref = getattr(x, "_m1_gslot_tail", None)
-    if tref is not None:
-        # x is the batch slice of a tensor with a shared gradient buffer (batch_tail): its consumers accumulate into the TAIL of that
-        # buffer (a gate forks the slice for its theta conv and the sigma product -- without this the fork opened a buffer of its own
-        # and autograd's slice backward added a zero-filled full-size tensor: a fill, a copy and an add over a res1 skip tensor)
-        outs = _Fanout.apply(x, k, tref, False)
-        for o in outs:
-            o._m1_gslot_tail = tref
-        return outs
-    slot = getattr(x, "_m1_gslot", None)
-    owner = slot is None
-    if owner:
-        slot = _GradSlot()
-    outs = _Fanout.apply(x, k, slot, owner)
-    for o in outs:
-        o._m1_gslot = slot
-    return outs
-
-
-class _BatchTail(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, start, slot):
-        ctx.slot, ctx.start, ctx.full_shape = slot, int(start), tuple(x.shape)
-        ctx.set_materialize_grads(False)
-        return x[int(start):]
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return None, None, None
-        buf = ctx.slot.buf
-        if buf is not None and tuple(buf.shape) == ctx.full_shape and g.dtype == buf.dtype:
-            tail = buf[ctx.start:]
-            if g.data_ptr() == tail.data_ptr() and tuple(g.shape) == tuple(tail.shape):
-                return buf, None, None                # the reader wrote straight into x's gradient buffer (_TailRef)
-        full = g.new_zeros(ctx.full_shape)
-        full[ctx.start:] = g
-        return full, None, None
-
-
-def batch_tail(x: torch.Tensor, start: int) -> torch.Tensor:
-    """``x[start:]`` along the batch axis for a reader that runs on the second of two stacked passes (M1Core.forward
-    ``tail_from``).  When ``x`` is a fanout alias the reader's backward kernel writes the tail of x's own gradient buffer:
-    autograd's slice backward (a zero-filled full-size tensor, a copy into it and an add into the buffer -- 4.5 passes over the
-    res0 / res1 skip tensors) disappears."""
-    slot = getattr(x, "_m1_gslot", None)
-    if slot is None or not torch.is_grad_enabled() or not x.requires_grad or _os.environ.get("M1_TAIL_SLOT", "1") == "0":
-        return x[int(start):]
-    y = _BatchTail.apply(x, int(start), slot)
-    y._m1_gslot_tail = _TailRef(slot, start, x.shape)
-    return y
-
-
-def _conv_ws(d, transposed: bool, role: int, device, zero: bool = False) -> torch.Tensor:
-    n = L.load().m1_conv_ws_bytes(C.byref(d), 1 if transposed else 0, role)
-    return (torch.zeros if zero else torch.empty)(max(int(n), 256), dtype=torch.uint8, device=device)
-
-
-# Packed weight panels are kept ON the weight tensor object, per (version, role, geometry), while the weights are
-# unchanged, so that the second pass of a core within one train step (prior and posterior each run twice,
-# networks.py:348-352) skips the pack.  Living on the tensor object they die with it (no address-reuse aliasing).
-_PANEL_EPOCH = [0]
-
-
-# Every cached panel is also REGISTERED: (id(weight), key) -> (weakref(weight), data_ptr, workspace, [device addresses of
-# its pack-job records]).  repack_all() refreshes all of them with one m1_pack_batch launch after an optimiser step.
-_PACK_REG: dict = {}
-_PACK_TABLE = [None]      # device int64 tensor of job-record addresses (rebuilt when the registry changes)
-
-
-def invalidate_panels() -> None:
-    """Call after anything that changes weights through raw pointers without re-packing (e.g. load_weights)."""
-    _PANEL_EPOCH[0] += 1
-    _PACK_REG.clear()
-    _PACK_TABLE[0] = None
-
-
-def repack_all() -> None:
-    """Re-pack every registered weight panel from the current weight values (one kernel launch).  The fused optimiser
-    calls this after its update, so the next step's convolutions find their panels already packed."""
-    dead = [k for k, (r, ptr, _, _) in _PACK_REG.items() if r() is None or r().data_ptr() != ptr]
-    for k in dead:
-        del _PACK_REG[k]
-        _PACK_TABLE[0] = None
-    if not _PACK_REG:
-        return
-    if _PACK_TABLE[0] is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("weight-panel registry changed during graph capture: run one eager step first")
-        ws0 = next(iter(_PACK_REG.values()))[2]
-        ptrs, blocks = [], [0]
-        for (r, _, _, jobs) in _PACK_REG.values():
-            per = max(1, int(r().numel()) // max(1, len(jobs)))          # weights per job (a dgrad panel per concat member)
-            for j in jobs:
-                ptrs.append(j)
-                blocks.append(blocks[-1] + min(512, max(1, -(-per // 16384))))   # ~8 segments of 8 weights per thread
-        _PACK_TABLE[0] = (torch.tensor(ptrs, dtype=torch.int64).to(ws0.device),
-                          torch.tensor(blocks, dtype=torch.int32).to(ws0.device), blocks[-1])
-    t, pref, total = _PACK_TABLE[0]
-    L.check(L.load().m1_pack_batch(_p(t), _p(pref), int(t.numel()), int(total), _stream()), "m1_pack_batch")
-
-
-def _panel_ws(w: torch.Tensor, d, transposed: bool, role: int, need_mask=None):
-    if not w.is_leaf:           # a derived weight (e.g. the zero-padded stem kernel): packed per call, never registered
-        return _conv_ws(d, transposed, role, w.device, zero=True), 0
-    store = getattr(w, "_m1_panels", None)
-    stamp = (_PANEL_EPOCH[0], w._version, w.data_ptr())
-    if store is None or store[0] != stamp:
-        store = (stamp, {})
-        try:
-            w._m1_panels = store
-        except Exception:  # noqa: BLE001 -- an object that cannot carry attributes: no caching
-            return _conv_ws(d, transposed, role, w.device), 0
-    key = (role, transposed, d.N, d.D, d.H, d.W, d.kd, d.kh, d.kw, d.sd, d.sh, d.sw, d.dtype,
-           tuple(d.src[i].C for i in range(d.nsrc)), need_mask)
-    hit = store[1].get(key)
-    if hit is not None:
-        return hit, 1
-    ws = _conv_ws(d, transposed, role, w.device, zero=True)     # zero: unfilled job records must read as empty
-    store[1][key] = ws
-    out = (C.c_void_p * L.M1_MAX_SRC)()
-    n = L.load().m1_conv_pack_jobs(C.byref(d), 1 if transposed else 0, role, _p(ws), out)
-    if n > 0:
-        _PACK_REG[(id(w), key)] = (weakref.ref(w), w.data_ptr(), ws, [int(out[i]) for i in range(n)])
-        _PACK_TABLE[0] = None
-    return ws, 0
+def _sinks(*params):
+    """(buffers, accumulate, autograd_returns) for the parameter gradients one backward kernel writes with ONE accumulate flag: all
+    of them live in the flat buffer or none does (_sink); otherwise every parameter falls back to an fp32 temporary that autograd
+    receives (vectors -- a conv bias, psi's bias -- 1-D).  ``None`` parameters (a conv without bias) get (None, None)."""
+    bound = {getattr(p, "_m1_gsink", None) is not None for p in params if p is not None}
+    if len(bound) == 1:
+        out = [(None, 0, None) if p is None else _sink(p) for p in params]
+        return [o[0] for o in out], int(True in bound), [o[2] for o in out]
+    tmp = [None if p is None else torch.empty(p.shape if p.dim() > 1 else (p.numel(),), dtype=torch.float32, device=p.device)
+           for p in params]
+    return tmp, 0, list(tmp)
 
 
 def same_out(size: int, s: int) -> int:
@@ -625,6 +97,28 @@ def same_out(size: int, s: int) -> int:
 # InstanceNorm-backward sums from the epilogue of the data gradient that produces d(a) (m1_conv3d_dgrad_inbwd): "fused" counts the
 # data gradients that emitted them, "plain" those whose kernel has no such epilogue (the norm then runs its own reduction)
 _INBWD = {"on": _os.environ.get("M1_INBWD_FUSE", "1") != "0", "fused": 0, "plain": 0}
+
+
+def _dgrad_targets(ctx, srcs, first: int):
+    """(dsrc, ptrs, accs) of a conv's data gradient: per concat member the gradient tensor (its slot's buffer or a fresh one; None
+    when input ``first + i`` needs no gradient), its address and its accumulate flag."""
+    dsrc = []
+    ptrs = (C.c_void_p * len(srcs))()
+    accs = (C.c_int * len(srcs))()
+    for i, t in enumerate(srcs):
+        g = None
+        if ctx.needs_input_grad[first + i]:
+            g, accs[i] = _slot_target(ctx.gslots[i], t)
+        dsrc.append(g)
+        ptrs[i] = _p(g)
+    return dsrc, ptrs, accs
+
+
+def _dgrad_written(ctx, dsrc) -> None:
+    """After the launch that wrote ``dsrc``: see _slot_written."""
+    for slot, g in zip(ctx.gslots, dsrc):
+        if g is not None:
+            _slot_written(slot)
 
 
 class _Conv3d(torch.autograd.Function):
@@ -685,25 +179,13 @@ class _Conv3d(torch.autograd.Function):
         dw = db = None
         if ctx.needs_input_grad[0] or (ctx.has_bias and ctx.needs_input_grad[1]):
             dw, db = _wgrad_into_sinks(lib, d, dy, ctx.w_param, ctx.b_param if ctx.has_bias else None, ctx.transposed, st, srcs)
-        dsrc: List[Optional[torch.Tensor]] = []
-        ptrs = (C.c_void_p * len(srcs))()
-        accs = (C.c_int * len(srcs))()
-        any_d = False
-        for i, t in enumerate(srcs):
-            if ctx.needs_input_grad[6 + i]:
-                g, accs[i] = _slot_target(ctx.gslots[i], t)
-                dsrc.append(g)
-                ptrs[i] = g.data_ptr()
-                any_d = True
-            else:
-                dsrc.append(None)
-                ptrs[i] = None
+        dsrc, ptrs, accs = _dgrad_targets(ctx, srcs, 6)
+        any_d = any(g is not None for g in dsrc)
         if any_d and ctx.in_src is not None and accs[0] == 0:
             tok = ctx.in_src
             xs, stats, gamma, beta, slope = tok.src
             da = dsrc[0]
-            N, Cn = int(xs.shape[0]), int(xs.shape[-1])
-            V = xs.numel() // (N * Cn)
+            N, _, Cn = _nvc(xs)
             # partial rows: the library states how many the kernel may write (its epilogue tiles or the split-K finish chunks)
             nmax = int(lib.m1_conv3d_dgrad_inbwd_rows(C.byref(d)))
             part = torch.empty(N * nmax * Cn * 2 + N * Cn * 2 + 64, dtype=torch.float32, device=da.device)
@@ -722,76 +204,17 @@ class _Conv3d(torch.autograd.Function):
             fn = lib.m1_convT3d_dgrad if ctx.transposed else lib.m1_conv3d_dgrad
             ws, packed = _panel_ws(ctx.w_param, d, ctx.transposed, 1, tuple(bool(g is not None) for g in dsrc))
             L.check(fn(C.byref(d), _p(w), _p(dy), ptrs, accs, _p(ws), packed, st), f"m1_{name}_dgrad")
-            for i in range(len(srcs)):
-                if dsrc[i] is not None:
-                    _slot_written(ctx.gslots[i])
+            _dgrad_written(ctx, dsrc)
         return (dw, db, None, None, None, None, *dsrc)
 
 
-def _pair_panel_ws(w1: torch.Tensor, w4: torch.Tensor, d, role: int, need_mask=None):
-    """Packed panel of the conv1 || conv4 pair (built from BOTH weight tensors), cached on w4 while neither changes."""
-    if not (w1.is_leaf and w4.is_leaf):
-        return _conv_ws(d, False, role, w4.device, zero=True), 0
-    store = getattr(w4, "_m1_pair_panels", None)
-    stamp = (_PANEL_EPOCH[0], w1._version, w1.data_ptr(), w4._version, w4.data_ptr())
-    if store is None or store[0] != stamp:
-        store = (stamp, {})
-        w4._m1_pair_panels = store
-    key = ("pair", role, d.N, d.D, d.H, d.W, d.kd, d.kh, d.kw, d.sd, d.sh, d.sw, d.dtype, int(w1.shape[-1]),
-           tuple(d.src[i].C for i in range(d.nsrc)), need_mask)
-    hit = store[1].get(key)
-    if hit is not None:
-        return hit, 1
-    ws = _conv_ws(d, False, role, w4.device, zero=True)
-    store[1][key] = ws
-    out = (C.c_void_p * L.M1_MAX_SRC)()
-    n = L.load().m1_conv_pack_jobs(C.byref(d), 0, role, _p(ws), out)
-    if n > 0:
-        _PACK_REG[(id(w4), key)] = (weakref.ref(w4), w4.data_ptr(), ws, [int(out[i]) for i in range(n)])
-        _PACK_TABLE[0] = None
-    return ws, 0
-
-
 def _wgrad_into_sinks(lib, d, dy, w_param, b_param, transposed: bool, st, srcs=()):
-    """Weight (+ bias) gradient of a conv into the parameters' sinks (or fresh tensors): returns (dw, db) for autograd.
-
-    The kernels run in order on the caller's stream (weight gradients on streams of their own next to the data-gradient chain were
-    measured twice, rounds 2 and 3: 0 ... +4 % slower -- the kernels fill the machine, they do not wait on it -- and removed).  With
-    both gradients going to the flat buffer the folds of the per-split partial copies are queued (m1_wgrad_defer) and run in batches."""
-    wbuf, acc_w, dw = _sink(w_param)
-    bbuf, db = None, None
-    if b_param is not None:
-        bbuf, acc_b, db = _sink(b_param)
-        if acc_b != acc_w:      # both or neither live in the flat buffer; otherwise fall back to temporaries
-            wbuf, acc_w = torch.empty_like(w_param), 0
-            bbuf = torch.empty(int(bbuf.numel()), dtype=torch.float32, device=w_param.device)
-            dw, db = wbuf, bbuf
+    """Weight (+ bias) gradient of a conv into the parameters' sinks (or fresh tensors): returns (dw, db) for autograd.  Where and
+    when the kernel runs is streams.submit_wgrad's business."""
+    (wbuf, bbuf), acc_w, (dw, db) = _sinks(w_param, b_param)
     fn = lib.m1_convT3d_wgrad if transposed else lib.m1_conv3d_wgrad
-    flat = dw is None and db is None
     ws = _conv_ws(d, transposed, 2, w_param.device)
-    if flat and _FOLD["on"]:
-        cur_ = torch.cuda.current_stream(w_param.device)
-        if (_WGP["maxvox"] > 0 and _BRANCH["on"] and _BRANCH.get("origin") is not None and
-                int(d.N) * int(d.D) * int(d.H) * int(d.W) <= _WGP["maxvox"]):
-            # queued: launched on the fold stream with the next batch (operands referenced until then, see _run_deferred_wgrads)
-            _WGP["jobs"].append((fn, d, dy, wbuf, bbuf, ws, acc_w, tuple(srcs)))
-            _WGP["extra"].extend((t, cur_) for t in (dy, *srcs))
-        else:
-            lib.m1_wgrad_defer(1)
-            try:
-                L.check(fn(C.byref(d), _p(dy), _p(wbuf), _p(bbuf), _p(ws), acc_w, st), "m1_conv3d_wgrad")
-            finally:
-                lib.m1_wgrad_defer(0)
-        _FOLD["keep"].append((ws, cur_))
-        if transposed and bbuf is not None:
-            # the bias gradient of a transposed conv is queued with the folds (norm.hip: m1_colsum_defer): d(out) is read at the fold
-            _FOLD["keep"].append((dy, torch.cuda.current_stream(w_param.device)))
-        _FOLD["bytes"] += ws.numel() * ws.element_size()
-        if _BRANCH["on"] and ((_FOLD["async"] > 0 and len(_FOLD["keep"]) >= _FOLD["async"]) or
-                              (_FOLD["async_mb"] > 0 and _FOLD["bytes"] >= _FOLD["async_mb"] << 20)):
-            _fold_async()
-    else:
-        L.check(fn(C.byref(d), _p(dy), _p(wbuf), _p(bbuf), _p(ws), acc_w, st), "m1_conv3d_wgrad")
+    submit_wgrad(fn, d, dy, wbuf, bbuf, ws, acc_w, transposed, srcs, st, flat=dw is None and db is None)
     return dw, db
 
 
@@ -841,23 +264,12 @@ class _ConvPair(torch.autograd.Function):
         if ctx.needs_input_grad[iw] or ctx.needs_input_grad[iw + 1]:
             dw1, db1 = _wgrad_into_sinks(lib, _desc(srcs, ctx.c1, ctx.k, ctx.s), dy1, ctx.w1_param, ctx.b1_param, False, st, srcs)
         d = _desc(srcs, ctx.c1 + ctx.c4, ctx.k, ctx.s)
-        dsrc: List[Optional[torch.Tensor]] = []
-        ptrs = (C.c_void_p * len(srcs))()
-        accs = (C.c_int * len(srcs))()
-        any_d = False
-        for i, t in enumerate(srcs):
-            if ctx.needs_input_grad[isrc + i]:
-                g, accs[i] = _slot_target(ctx.gslots[i], t)
-                dsrc.append(g); ptrs[i] = g.data_ptr(); any_d = True
-            else:
-                dsrc.append(None); ptrs[i] = None
-        if any_d:
+        dsrc, ptrs, accs = _dgrad_targets(ctx, srcs, isrc)
+        if any(g is not None for g in dsrc):
             ws, packed = _pair_panel_ws(ctx.w1_param, ctx.w4_param, d, 1, tuple(bool(g is not None) for g in dsrc))
             L.check(lib.m1_conv3d_pair_dgrad(C.byref(d), _p(w1), _p(w4), ctx.c1, _p(dy1), _p(dy4), ptrs, accs, _p(ws), packed, st),
                     "m1_conv3d_pair_dgrad")
-            for i in range(len(srcs)):
-                if dsrc[i] is not None:
-                    _slot_written(ctx.gslots[i])
+            _dgrad_written(ctx, dsrc)
         return (dw1, db1, None, None, None, None, *dsrc)
 
 
@@ -962,8 +374,7 @@ def conv3d_transpose_same(srcs, w, b, k, s):
 # ---------------------------------------------------------------------------------------------------------
 def instnorm_stats(x: torch.Tensor) -> torch.Tensor:
     _req(x)
-    N, Cn = int(x.shape[0]), int(x.shape[-1])
-    V = x.numel() // (N * Cn)
+    N, V, Cn = _nvc(x)
     stats = torch.empty((N, Cn, 2), dtype=torch.float32, device=x.device)
     ws = _ws(N, V, Cn, 2, x.device)
     L.check(L.load().m1_instnorm_stats(_p(x), N, V, Cn, _dt(x), IN_EPS, _p(stats), _p(ws), _stream()), "m1_instnorm_stats")
@@ -984,8 +395,7 @@ class _InstNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, slope, stats, tok=None):
         _req(x, gamma, beta)
-        N, Cn = int(x.shape[0]), int(x.shape[-1])
-        V = x.numel() // (N * Cn)
+        N, V, Cn = _nvc(x)
         if stats is None:
             stats = instnorm_stats(x)
         y = torch.empty_like(x)
@@ -1001,14 +411,9 @@ class _InstNormAct(torch.autograd.Function):
     def backward(ctx, dy):
         x, stats, gamma, beta = ctx.saved_tensors
         dy = dy.contiguous()
-        N, Cn = int(x.shape[0]), int(x.shape[-1])
-        V = x.numel() // (N * Cn)
+        N, V, Cn = _nvc(x)
         dx = torch.empty_like(x)
-        gbuf, acc, dg = _sink(ctx.g_param)
-        bbuf, acc2, db = _sink(ctx.b_param)
-        if acc != acc2:
-            gbuf, bbuf, acc = torch.empty_like(gamma), torch.empty_like(beta), 0
-            dg, db = gbuf, bbuf
+        (gbuf, bbuf), acc, (dg, db) = _sinks(ctx.g_param, ctx.b_param)
         tok = ctx.tok
         pp = tok.partials if tok is not None else None
         if tok is not None:
@@ -1071,8 +476,7 @@ class _SECombine(torch.autograd.Function):
     def forward(ctx, y3, y4, g3, b3, g4, b4, W6, b6, W7, b7, drop_rate, rng, layer_id, s3, s4, gate, dup=False):
         _req(y3, y4, g3, b3, g4, b4, W6, b6, W7, b7)
         lib = L.load()
-        N, Fn = int(y3.shape[0]), int(y3.shape[-1])
-        V = y3.numel() // (N * Fn)
+        N, V, Fn = _nvc(y3)
         Fr = int(W6.shape[-1])
         st = _stream()
         ident = g4 is None and b4 is None            # network_blocks.py:63 false branch: y4 is the block input, no norm4
@@ -1103,10 +507,9 @@ class _SECombine(torch.autograd.Function):
         ctx.ident, ctx.dup = ident, dup
         if ident:
             ctx.save_for_backward(y3, y4, s3, g3, b3, W6, W7, hidden, g)
-            ctx.params = (g3, b3, W6, b6, W7, b7)
         else:
             ctx.save_for_backward(y3, y4, s3, s4, g3, b3, g4, b4, W6, W7, hidden, g)
-            ctx.params = (g3, b3, g4, b4, W6, b6, W7, b7)
+        ctx.params = (g3, b3, g4, b4, W6, b6, W7, b7)             # (g4 = b4 = None on the identity residual)
         ctx.mask = mask
         ctx.rng, ctx.drop_rate, ctx.layer_id = rng, float(drop_rate), int(layer_id)
         return out
@@ -1120,22 +523,12 @@ class _SECombine(torch.autograd.Function):
         else:
             y3, y4, s3, s4, g3, b3, g4, b4, W6, W7, hidden, g = ctx.saved_tensors
         dout = dout.contiguous()
-        N, Fn = int(y3.shape[0]), int(y3.shape[-1])
-        V = y3.numel() // (N * Fn)
+        N, V, Fn = _nvc(y3)
         Fr = int(W6.shape[-1])
         st = _stream()
         dev = y3.device
         dy3, dy4 = torch.empty_like(y3), torch.empty_like(y4)
-        sinks = [_sink(p) for p in ctx.params]
-        acc = sinks[0][1]
-        if any(sk[1] != acc for sk in sinks):
-            sinks = [(t, 0, t) for t in (torch.empty_like(p, dtype=torch.float32) for p in ctx.params)]
-            acc = 0
-        if ctx.ident:
-            (bg3, _, rg3), (bb3, _, rb3), (bW6, _, rW6), (bb6, _, rb6), (bW7, _, rW7), (bb7, _, rb7) = sinks
-            bg4 = bb4 = rg4 = rb4 = None
-        else:
-            (bg3, _, rg3), (bb3, _, rb3), (bg4, _, rg4), (bb4, _, rb4), (bW6, _, rW6), (bb6, _, rb6), (bW7, _, rW7), (bb7, _, rb7) = sinks
+        (bg3, bb3, bg4, bb4, bW6, bb6, bW7, bb7), acc, rets = _sinks(*ctx.params)
         dg = torch.empty(Fn + Fr, dtype=torch.float32, device=dev)
         ws = _ws(N, V, Fn, 5, dev)
         bwd = lib.m1_se_combine_dup_bwd if ctx.dup else lib.m1_se_combine_bwd
@@ -1151,7 +544,7 @@ class _SECombine(torch.autograd.Function):
         else:
             L.check(lib.m1_se_gate_bwd(_p(b3), _p(W6), _p(W7), _p(hidden), _p(g), _p(dg), Fn, Fr, _p(bb3), _p(bW6), _p(bb6),
                                        _p(bW7), _p(bb7), acc, st), "m1_se_gate_bwd")
-        return dy3, dy4, rg3, rb3, rg4, rb4, rW6, rb6, rW7, rb7, None, None, None, None, None, None, None
+        return (dy3, dy4, *rets, None, None, None, None, None, None, None)
 
 
 def se_combine(y3, y4, g3, b3, g4, b4, W6, b6, W7, b7, drop_rate=0.0, rng=None, layer_id=0, stats3=None, stats4=None,
@@ -1187,6 +580,30 @@ def se_gate_batch(params):
 # ---------------------------------------------------------------------------------------------------------
 # attention-gate pieces
 # ---------------------------------------------------------------------------------------------------------
+def _gate_sigma_bwd(ctx, theta, phi, wpsi, sigma, dsigma):
+    """(dtheta, dphi, dw, db) of sigma = gate_sigma(theta, phi, psi) for a contiguous ``dsigma`` (m1_gate_sigma_bwd)."""
+    N, Dt, Ht, Wt, Cn = (int(v) for v in theta.shape)
+    Dp, Hp, Wp = (int(v) for v in phi.shape[1:4])
+    dtheta, dphi = torch.empty_like(theta), torch.empty_like(phi)
+    (wbuf, bbuf), acc, (dw, db) = _sinks(ctx.w_param, ctx.b_param)
+    ws = _ws(N, Dt * Ht * Wt, Cn, 2, theta.device)
+    L.check(L.load().m1_gate_sigma_bwd(_p(theta), _p(phi), _p(wpsi), _p(sigma), _p(dsigma), _p(dtheta), _p(dphi), _p(wbuf),
+                                       _p(bbuf), N, Dt, Ht, Wt, Dp, Hp, Wp, Cn, _dt(theta), _p(ws), acc, _stream()),
+            "m1_gate_sigma_bwd")
+    return dtheta, dphi, dw, db
+
+
+def _mul_sigma_bwd(ctx, x, sigma, dy):
+    """(dx, dsigma) of y = mul_sigma(x, sigma) for a contiguous ``dy``; dx goes to x's gradient slot (m1_mul_sigma_bwd)."""
+    N, D, H, W, Cn = (int(v) for v in x.shape)
+    dsig = torch.empty_like(sigma)
+    dx, acc = _slot_target(ctx.gslot, x)
+    L.check(L.load().m1_mul_sigma_bwd(_p(x), _p(sigma), _p(dy), _p(dx), _p(dsig), N, D, H, W, Cn, *ctx.ss, _dt(x), acc,
+                                      _stream()), "m1_mul_sigma_bwd")
+    _slot_written(ctx.gslot)
+    return dx, dsig
+
+
 class _GateSigma(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, phi, wpsi, bpsi):
@@ -1202,21 +619,7 @@ class _GateSigma(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dsigma):
-        theta, phi, wpsi, sigma = ctx.saved_tensors
-        dsigma = dsigma.contiguous()
-        N, Dt, Ht, Wt, Cn = (int(v) for v in theta.shape)
-        Dp, Hp, Wp = (int(v) for v in phi.shape[1:4])
-        dtheta, dphi = torch.empty_like(theta), torch.empty_like(phi)
-        wbuf, acc, dw = _sink(ctx.w_param)
-        bbuf, acc2, db = _sink(ctx.b_param)
-        if acc != acc2:
-            wbuf, bbuf, acc = torch.empty_like(wpsi), torch.empty(1, dtype=torch.float32, device=theta.device), 0
-            dw, db = wbuf, bbuf
-        ws = _ws(N, Dt * Ht * Wt, Cn, 2, theta.device)
-        L.check(L.load().m1_gate_sigma_bwd(_p(theta), _p(phi), _p(wpsi), _p(sigma), _p(dsigma), _p(dtheta), _p(dphi), _p(wbuf),
-                                           _p(bbuf), N, Dt, Ht, Wt, Dp, Hp, Wp, Cn, _dt(theta), _p(ws), acc, _stream()),
-                "m1_gate_sigma_bwd")
-        return dtheta, dphi, dw, db
+        return _gate_sigma_bwd(ctx, *ctx.saved_tensors, dsigma.contiguous())
 
 
 def gate_sigma(theta, phi, wpsi, bpsi):
@@ -1238,15 +641,7 @@ class _MulSigma(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, sigma = ctx.saved_tensors
-        dy = dy.contiguous()
-        N, D, H, W, Cn = (int(v) for v in x.shape)
-        dsig = torch.empty_like(sigma)
-        dx, acc = _slot_target(ctx.gslot, x)
-        L.check(L.load().m1_mul_sigma_bwd(_p(x), _p(sigma), _p(dy), _p(dx), _p(dsig), N, D, H, W, Cn, *ctx.ss, _dt(x), acc,
-                                          _stream()), "m1_mul_sigma_bwd")
-        _slot_written(ctx.gslot)
-        return dx, dsig, None
+        return (*_mul_sigma_bwd(ctx, *ctx.saved_tensors, dy.contiguous()), None)
 
 
 def mul_sigma(x, sigma, ss=(1, 1, 1)):
@@ -1280,28 +675,10 @@ class _GateSigmaMul(torch.autograd.Function):
         theta, phi, wpsi, sigma, x = ctx.saved_tensors
         if dy is None:                                       # (only sigma was used downstream)
             dy = torch.zeros_like(x)
-        dy = dy.contiguous()
-        lib = L.load()
-        N, D, H, W, Cx = (int(v) for v in x.shape)
-        dsig = torch.empty_like(sigma)
-        dx, acc_x = _slot_target(ctx.gslot, x)
-        L.check(lib.m1_mul_sigma_bwd(_p(x), _p(sigma), _p(dy), _p(dx), _p(dsig), N, D, H, W, Cx, *ctx.ss, _dt(x), acc_x, _stream()),
-                "m1_mul_sigma_bwd")
-        _slot_written(ctx.gslot)
+        dx, dsig = _mul_sigma_bwd(ctx, x, sigma, dy.contiguous())
         if dsigma_out is not None:                           # sigma is an output of the block too (B:130): its own gradient, if any
             dsig = dsig + dsigma_out.to(dsig.dtype)
-        _, Dt, Ht, Wt, Ci = (int(v) for v in theta.shape)
-        Dp, Hp, Wp = (int(v) for v in phi.shape[1:4])
-        dtheta, dphi = torch.empty_like(theta), torch.empty_like(phi)
-        wbuf, acc, dw = _sink(ctx.w_param)
-        bbuf, acc_b, db = _sink(ctx.b_param)
-        if acc_b != acc:
-            wbuf, bbuf, acc = torch.empty_like(wpsi), torch.empty(1, dtype=torch.float32, device=theta.device), 0
-            dw, db = wbuf, bbuf
-        ws = _ws(N, Dt * Ht * Wt, Ci, 2, theta.device)
-        L.check(lib.m1_gate_sigma_bwd(_p(theta), _p(phi), _p(wpsi), _p(sigma), _p(dsig), _p(dtheta), _p(dphi), _p(wbuf), _p(bbuf),
-                                      N, Dt, Ht, Wt, Dp, Hp, Wp, Ci, _dt(theta), _p(ws), acc, _stream()), "m1_gate_sigma_bwd")
-        return dtheta, dphi, dw, db, dx, None
+        return (*_gate_sigma_bwd(ctx, theta, phi, wpsi, sigma, dsig), dx, None)
 
 
 _GATE_FUSED = {"on": _os.environ.get("M1_GATE_FWD_FUSED", "1") != "0"}
@@ -1327,8 +704,7 @@ class _LatentSample(torch.autograd.Function):
         _req(ml, eps)
         if eps is not None and eps.dtype != ml.dtype:
             raise RuntimeError(f"latent_sample: eps is {eps.dtype}, the head output {ml.dtype} (the kernel reads both as one type)")
-        N = int(ml.shape[0]); Lc = int(ml.shape[-1]) // 2
-        V = ml.numel() // (N * 2 * Lc)
+        N, V, Lc = _nvc(ml, 2)
         # the kernel reads eps for every sample (modes 0 / 1 -- mode 1 ignores the values) or for the first half of the batch only
         # (mode 2, stacked passes): a draw tensor of another size would be read out of bounds
         need = ml.numel() // 4 if int(mode) == 2 else ml.numel() // 2
@@ -1347,8 +723,7 @@ class _LatentSample(torch.autograd.Function):
     def backward(ctx, dz):
         ml, eps = ctx.saved_tensors
         dz = dz.contiguous()
-        N = int(ml.shape[0]); Lc = int(ml.shape[-1]) // 2
-        V = ml.numel() // (N * 2 * Lc)
+        N, V, Lc = _nvc(ml, 2)
         dml = torch.empty_like(ml)
         L.check(L.load().m1_latent_sample_bwd(_p(ml), _p(eps) if eps.numel() else None, _p(dz), _p(dml), N, V, Lc, ctx.mode,
                                               _dt(ml), _stream()), "m1_latent_sample_bwd")
@@ -1361,8 +736,7 @@ class _LatentSampleRng(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ml, rng, stream_id, mode):
         _req(ml, rng)
-        N = int(ml.shape[0]); Lc = int(ml.shape[-1]) // 2
-        V = ml.numel() // (N * 2 * Lc)
+        N, V, Lc = _nvc(ml, 2)
         if int(mode) == 2 and N % 2:
             raise RuntimeError("latent_sample: stacked mode needs an even batch")
         z = torch.empty((*ml.shape[:-1], Lc), dtype=ml.dtype, device=ml.device)
@@ -1376,8 +750,7 @@ class _LatentSampleRng(torch.autograd.Function):
     def backward(ctx, dz):
         (ml,) = ctx.saved_tensors
         dz = dz.contiguous()
-        N = int(ml.shape[0]); Lc = int(ml.shape[-1]) // 2
-        V = ml.numel() // (N * 2 * Lc)
+        N, V, Lc = _nvc(ml, 2)
         dml = torch.empty_like(ml)
         L.check(L.load().m1_latent_sample_rng_bwd(_p(ml), _p(ctx.rng), ctx.stream_id, _p(dz), _p(dml), N, V, Lc, ctx.mode, _dt(ml),
                                                   _stream()), "m1_latent_sample_rng_bwd")
@@ -1398,11 +771,10 @@ class _KL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mq, mp, first):
         _req(mq, mp)
-        Nall = int(mq.shape[0]); Lc = int(mq.shape[-1]) // 2
+        Nall, V, Lc = _nvc(mq, 2)
         N = Nall if first is None else int(first)
         if not (0 < N <= Nall) or mq.shape != mp.shape:
             raise RuntimeError("kl_mvn_diag: both heads must have one shape, `first` within the batch")
-        V = mq.numel() // (Nall * 2 * Lc)
         kl = torch.empty(1, dtype=torch.float32, device=mq.device)
         L.check(L.load().m1_kl_fwd(_p(mq), _p(mp), _p(kl), N, V, Lc, _dt(mq), _stream()), "m1_kl_fwd")
         ctx.save_for_backward(mq, mp)
@@ -1413,8 +785,7 @@ class _KL(torch.autograd.Function):
     def backward(ctx, dkl):
         mq, mp = ctx.saved_tensors
         dkl = dkl.contiguous().float()
-        Nall = int(mq.shape[0]); Lc = int(mq.shape[-1]) // 2
-        V = mq.numel() // (Nall * 2 * Lc)
+        Nall, V, Lc = _nvc(mq, 2)
         dq, dp = torch.empty_like(mq), torch.empty_like(mp)
         L.check(L.load().m1_kl_bwd_first(_p(mq), _p(mp), _p(dkl), _p(dq), _p(dp), ctx.first, V, Lc, Nall, _dt(mq), _stream()), "m1_kl_bwd")
         return dq, dp, None

@@ -221,7 +221,7 @@ class Adam:
         ops.adam_amsgrad_(f.flat, f.grad, self.m, self.v, self.vhat, f.n_kernel, f.n_bias, self.l2_kernel, self.l2_bias,
                           self.grad_scale, self.lr_dev, self.beta_1, self.beta_2, self.epsilon, self.step_dev)
         ops.step_advance(self.step_dev, None)
-        ops.repack_all()                 # weights changed behind torch's back: refresh every cached weight panel
+        ops.repack_all()                 # weights changed behind torch's back: refresh every cached weight panel (hip/panels.py)
 
     def step(self):
         self.set_lr_device()

@@ -279,7 +279,7 @@ class M1Core(nn.Module):
         # networks.py:574-576
         x_raw, s0 = self.conve0(inputs, stats=True)
         x = self.norme0(x_raw, 0.1, s0)
-        # A tensor read by several layers is handed out as one alias per reader (ops.fanout): the readers' backward kernels
+        # A tensor read by several layers is handed out as one alias per reader (ops.fanout, hip/gradslot.py): the readers' backward kernels
         # then sum its gradient in one buffer instead of autograd adding per-reader gradient tensors.
         split = lambda t, on: fo(t, 2) if on else (t, None)
         # networks.py:579-582 (dropout fused into the block's last kernel)
@@ -296,7 +296,7 @@ class M1Core(nn.Module):
         n_m = n_stage + (1 if n_stage > 0 else 0) + ((1 if n_lat > 0 else 0) + (1 if n_up > 0 else 0) if prob else 0)
         m_use = list(fo(convm, n_m)) if n_m > 1 else [convm]
         # networks.py:585-588
-        # the gates depend on the encoder only: each runs on a side stream of its own, next to the decoder (ops.branch),
+        # the gates depend on the encoder only: each runs on a side stream of its own, next to the decoder (ops.branch, hip/streams.py),
         # and is joined where the decoder first reads it
         dvc = convm.device
         att_conv = [None] * 4

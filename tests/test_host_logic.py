@@ -525,3 +525,42 @@ def test_config_switches_are_set_and_restored_through_the_abi():
     assert ops.config_get("M1_T3_MIN_BLOCKS") == 128
     ops.config_unset("M1_T3_MIN_BLOCKS")
     assert ops.config_get("M1_T3_MIN_BLOCKS") == int(os.environ["M1_T3_MIN_BLOCKS"])
+
+
+def test_parameter_gradient_sinks_are_all_flat_or_all_temporaries():
+    """ops._sinks, the rule every backward with parameter gradients follows (conv, InstanceNorm, SE, gates): its kernel takes ONE
+    accumulate flag, so either every parameter's gradient is accumulated in its flat-buffer view (``_m1_gsink``; autograd gets None,
+    ``_m1_live`` marks the parameter) or every one goes to a fresh fp32 tensor that autograd receives."""
+    ops = PKG.hip.ops
+
+    def params(bound):
+        ps = [torch.nn.Parameter(torch.zeros(3, 1, 1, 4, 2)), torch.nn.Parameter(torch.zeros(2)), torch.nn.Parameter(torch.zeros(1))]
+        for p, b in zip(ps, bound):
+            if b:
+                p._m1_gsink = torch.zeros_like(p)
+        return ps
+    # all in sinks: the sink views themselves, accumulate, nothing for autograd, every parameter marked live
+    ps = params((1, 1, 1))
+    bufs, acc, rets = ops._sinks(*ps)
+    assert acc == 1 and all(b is p._m1_gsink for b, p in zip(bufs, ps)) and rets == [None, None, None]
+    assert all(getattr(p, "_m1_live", False) is True for p in ps)
+    # none in sinks: fp32 tensors of the parameters' shapes, overwritten, handed to autograd
+    ps = params((0, 0, 0))
+    bufs, acc, rets = ops._sinks(*ps)
+    assert acc == 0 and all(r is b for r, b in zip(rets, bufs))
+    assert [(tuple(b.shape), b.dtype) for b in bufs] == [(tuple(p.shape), torch.float32) for p in ps]
+    assert not any(hasattr(p, "_m1_live") for p in ps)
+    # mixed: temporaries for ALL of them (vectors 1-D, of numel elements), no sink touched, so no parameter marked live here
+    for bound in ((1, 0, 0), (0, 1, 1), (1, 1, 0)):
+        ps = params(bound)
+        bufs, acc, rets = ops._sinks(*ps)
+        assert acc == 0 and all(r is b for r, b in zip(rets, bufs))
+        assert [(tuple(b.shape), b.dtype) for b in bufs] == [((3, 1, 1, 4, 2), torch.float32), ((2,), torch.float32), ((1,), torch.float32)]
+        assert not any(b is getattr(p, "_m1_gsink", None) for b, p in zip(bufs, ps))
+        assert not any(hasattr(p, "_m1_live") for p in ps)
+    # a conv without bias: the missing parameter takes no part in the rule and gets nothing
+    w = params((1, 0, 0))[0]
+    assert ops._sinks(w, None) == ([w._m1_gsink, None], 1, [None, None]) and w._m1_live is True
+    w = params((0, 0, 0))[0]
+    (wbuf, bbuf), acc, (dw, db) = ops._sinks(w, None)
+    assert acc == 0 and dw is wbuf and tuple(wbuf.shape) == tuple(w.shape) and bbuf is None and db is None
