@@ -181,6 +181,9 @@ static inline int m1_check_launch() {
     return e == hipSuccess ? M1_OK : M1_ERR_LAUNCH;
 }
 static inline long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
+// raise the dynamic-LDS limit of `kern` to `bytes`, once per kernel pointer (config.hip): call directly before a launch that needs
+// more than 48 KB.  M1_OK or M1_ERR_LAUNCH.
+int m1_allow_dynamic_lds(const void* kern, int bytes);
 
 // kernel-choice log (prof.hip; m1_debug_kernels in include/m1hip.h): the dispatch names the kernel behind every conv-like launch so
 // that a test of a special kernel can assert it ran (a declined shape would otherwise compare the generic kernel with itself)

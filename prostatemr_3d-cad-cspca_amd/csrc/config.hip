@@ -1,4 +1,5 @@
-// config.hip -- the table behind M1_CFG (common.h) and m1_config_set / m1_config_get / m1_config_unset (include/m1hip.h).
+// config.hip -- the table behind M1_CFG (common.h) and m1_config_set / m1_config_get / m1_config_unset (include/m1hip.h);
+// the dynamic-LDS opt-in of the launchers (m1_allow_dynamic_lds).
 #include "common.h"
 #include <mutex>
 #include <string.h>
@@ -52,4 +53,16 @@ extern "C" int m1_config_get(const char* name, int* value) {
             *value = g_cfg[i].v; return M1_OK;
         }
     return M1_ERR_UNSUPPORTED;
+}
+
+// every kernel of the library that launches with more than 48 KB of dynamic LDS fits (about 210 instantiations)
+#define M1_LDS_MAX 256
+int m1_allow_dynamic_lds(const void* kern, int bytes) {
+    static const void* done[M1_LDS_MAX]; static int ndone = 0;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    for (int q = 0; q < ndone; ++q) if (done[q] == kern) return M1_OK;
+    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return M1_ERR_LAUNCH;
+    if (ndone < M1_LDS_MAX) done[ndone++] = kern;
+    return M1_OK;
 }

@@ -27,33 +27,6 @@
 #include <stdlib.h>
 #include <stdio.h>
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __attribute__((aligned(64))) unsigned int m1_zero_page_h[16];
-
-__device__ __forceinline__ void glds16h(const void* g, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ u32x4_t lds_read128h(unsigned lds_addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_waith(u32x4_t& v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)); }
-__device__ __forceinline__ void lds_tieh(u32x4_t& v) { asm volatile("" : "+v"(v)); }     // no instruction: ordering only
-__device__ __forceinline__ void wait_vmh(int n) {
-    switch (n) {
-#define HW(N_) case N_: asm volatile("s_waitcnt vmcnt(" #N_ ")" ::: "memory"); break;
-        HW(0) HW(1) HW(2) HW(3) HW(4) HW(5) HW(6) HW(7) HW(8) HW(9) HW(10) HW(11) HW(12) HW(13) HW(14) HW(15) HW(16)
-        HW(17) HW(18) HW(19) HW(20) HW(21) HW(22) HW(23) HW(24) HW(25) HW(26) HW(27) HW(28) HW(29) HW(30) HW(31) HW(32)
-        HW(33) HW(34) HW(35) HW(36) HW(37) HW(38) HW(39) HW(40)
-#undef HW
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
 #define HL_MAX_XIT 10        // LDS-DMA pieces per thread for one input tile
 #define HL_MAX_CH 18         // K chunks (of 32) whose fragment offsets live in registers (18 = 9 taps x 64 channels; the run-time variant on 512 threads sits at the 256-VGPR limit)
 
@@ -79,23 +52,12 @@ struct HaloP {
 __device__ __forceinline__ int x_swz(int row, int sl, int spr) {
     return spr == 8 ? (sl ^ (row & 7)) : (spr == 4 ? (sl ^ ((row >> 1) & 3)) : sl);
 }
-__device__ __forceinline__ int b_swz(int row, int seg) { return seg ^ ((-(row >> 2)) & 3); }
 
-// pack two floats to bf16x2 (round to nearest even): one v_cvt_pk_bf16_f32
-typedef __attribute__((ext_vector_type(2))) __bf16 hbf2_t;
-typedef __attribute__((ext_vector_type(2))) float hf2_t;
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((hf2_t){a, b}, hbf2_t));
-}
 // 8-byte load the compiler does not track (its own bookkeeping would wait vmcnt(0) at the first use, draining the DMA issued behind it)
 __device__ __forceinline__ unsigned long long gload8_untracked(const void* p) {
     unsigned long long v;
     asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(v) : "v"(p) : "memory");
     return v;
-}
-template <int N_> __device__ __forceinline__ void wait_vm_c() {
-    static_assert(N_ >= 0 && N_ <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
 }
 
 // NCH / NXIT > 0: the number of K chunks / of LDS-DMA pieces per thread are compile-time (the common layer shapes: straight-line
@@ -117,7 +79,7 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
     const MfmaP& m = p.m;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int oc0 = blockIdx.x * BN;
-    const unsigned char* zero_pg = reinterpret_cast<const unsigned char*>(m1_zero_page_h);
+    const unsigned char* zero_pg = reinterpret_cast<const unsigned char*>(m1_zero_page);
     const int fr = lane & 15, fs = lane >> 4;
     const int spt_sh = p.spr_sh;                                      // log2 of the 16-byte K segments per tap (= slots per row)
 
@@ -127,7 +89,7 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
         const int nslot = p.nchunks * BN * 4;
         for (int q0 = 0; q0 < nslot; q0 += NTHR) {
             const int q = q0 + tid;                                   // LDS slot: chunk, oc row, physical 16-byte slot
-            const int ch = q / (BN * 4), r = (q / 4) % BN, s = b_swz(r, q & 3);
+            const int ch = q / (BN * 4), r = (q / 4) % BN, s = m1_swz64(r, q & 3);
             const unsigned char* src;
             if constexpr (CLS) {         // class c's matrix [OCpad][kpad_c] sits at cls_woff[c]
                 const int c = cls_of(ch), lo = cls_lo(c), kp = m.cls_kpad[c];
@@ -135,7 +97,7 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
             } else
             src = (q < nslot) ? reinterpret_cast<const unsigned char*>(wp + (long long)(oc0 + r) * p.kpad + (ch * 4 + s) * SEG)
                                                    : zero_pg;
-            if (q0 + wave * 64 < nslot) glds16h(src, Bs + (q0 + wave * 64) * 16);
+            if (q0 + wave * 64 < nslot) m1_glds16(src, Bs + (q0 + wave * 64) * 16);
         }
     }
 
@@ -185,7 +147,7 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
                     const long long real = (long long)(x_ptr[it] + (long long)lin0 * x_C[it]);
                     const int ok = x_pk[it] >= 0;
                     const unsigned char* src = reinterpret_cast<const unsigned char*>(zp + ((real - zp) & -(long long)ok));
-                    glds16h(src, Xs + (it * NTHR + wave * 64) * 16);
+                    m1_glds16(src, Xs + (it * NTHR + wave * 64) * 16);
                 }
             }
         } else {
@@ -199,7 +161,7 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
                                    (int)((unsigned)(iw0 + ww) < (unsigned)m.IW);
                     const long long real = (long long)(x_ptr[it] + (long long)lin0 * x_C[it]);
                     const unsigned char* src = reinterpret_cast<const unsigned char*>(zp + ((real - zp) & -(long long)ok));
-                    glds16h(src, Xs + (it * NTHR + wave * 64) * 16);
+                    m1_glds16(src, Xs + (it * NTHR + wave * 64) * 16);
                 }
             }
         }
@@ -230,7 +192,7 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
     }
     unsigned b_off[TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) b_off[j] = lds0 + (j * 16 + fr) * 64 + b_swz(fr, fs) * 16;
+    for (int j = 0; j < TN; ++j) b_off[j] = lds0 + (j * 16 + fr) * 64 + m1_swz64(fr, fs) * 16;
 
     // ---- epilogue invariants.  The weights are the MFMA's A operand, so a lane ends up with FOUR CONSECUTIVE OUTPUT
     // CHANNELS (oc = j*16 + fs*4 + r) of ONE voxel (wave*32 + i*16 + fr): bias, rounding, the optional add, the statistics
@@ -328,8 +290,8 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
     int st = 0;
     for (; c_kt < p.ntiles; advance(c_kt, c_tw, c_th, c_od, c_n)) {
         if (want_stats) { for (; cur_n < c_n; ++cur_n) flush(cur_n); }
-        if constexpr (RT) wait_vmh(npiece * (S - 2));
-        else { if (S == 2) wait_vm_c<0>(); else if (S == 3) wait_vm_c<NXIT>(); else wait_vm_c<2 * NXIT>(); }
+        if constexpr (RT) m1_wait_vm<40>(npiece * (S - 2));
+        else { if (S == 2) m1_wait_vm_imm<0>(); else if (S == 3) m1_wait_vm_imm<NXIT>(); else m1_wait_vm_imm<2 * NXIT>(); }
         __builtin_amdgcn_s_barrier();
         // out += launches: fetch what is there BEFORE the next tile's DMA is issued -- loads retire in order, so a load issued
         // behind the DMA could only be waited for together with it
@@ -372,23 +334,23 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
             for (int j = 0; j < TN; ++j) acc[c][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         u32x4_t af[2][TM], bf[2][TN];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) af[0][i] = lds_read128h(a_off[0][i] + sb);
+        for (int i = 0; i < TM; ++i) af[0][i] = m1_lds_read128(a_off[0][i] + sb);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bf[0][j] = lds_read128h(b_off[j]);
+        for (int j = 0; j < TN; ++j) bf[0][j] = m1_lds_read128(b_off[j]);
 #pragma unroll
         for (int q = 0; q < CH; ++q) {
             if (!RT || q < nchunks) {
                 const int cur = q & 1;
-                lds_waith(af[cur][0]);
+                m1_lds_wait(af[cur][0]);
 #pragma unroll
-                for (int i = 1; i < TM; ++i) lds_tieh(af[cur][i]);
+                for (int i = 1; i < TM; ++i) m1_lds_tie(af[cur][i]);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) lds_tieh(bf[cur][j]);
+                for (int j = 0; j < TN; ++j) m1_lds_tie(bf[cur][j]);
                 if (q + 1 < CH && (!RT || q + 1 < nchunks)) {
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) af[cur ^ 1][i] = lds_read128h(a_off[q + 1 < CH ? q + 1 : q][i] + sb);
+                    for (int i = 0; i < TM; ++i) af[cur ^ 1][i] = m1_lds_read128(a_off[q + 1 < CH ? q + 1 : q][i] + sb);
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) bf[cur ^ 1][j] = lds_read128h(b_off[j] + (q + 1) * BN * 64);
+                    for (int j = 0; j < TN; ++j) bf[cur ^ 1][j] = m1_lds_read128(b_off[j] + (q + 1) * BN * 64);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -403,7 +365,7 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
 
         // ---- epilogue in registers ----
         if (any_acc || ib) {      // the fetched values: everything but the DMA pieces issued behind them has landed
-            if constexpr (RT) wait_vm_c<0>(); else wait_vm_c<NXIT>();
+            if constexpr (RT) m1_wait_vm_imm<0>(); else m1_wait_vm_imm<NXIT>();
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -433,12 +395,12 @@ __global__ void __launch_bounds__(NTHR) conv_halo_kernel(HaloP p) {
                         const uint2 ov = make_uint2((unsigned)oldv[c][i][j], (unsigned)(oldv[c][i][j] >> 32));
                         const float b[4] = {__uint_as_float(ov.x << 16), __uint_as_float(ov.x & 0xffff0000u),
                                             __uint_as_float(ov.y << 16), __uint_as_float(ov.y & 0xffff0000u)};
-                        const unsigned r01 = cvt_pk_bf16(v[0], v[1]), r23 = cvt_pk_bf16(v[2], v[3]);
+                        const unsigned r01 = m1_cvt_pk_bf16(v[0], v[1]), r23 = m1_cvt_pk_bf16(v[2], v[3]);
                         v[0] = __uint_as_float(r01 << 16) + b[0]; v[1] = __uint_as_float(r01 & 0xffff0000u) + b[1];
                         v[2] = __uint_as_float(r23 << 16) + b[2]; v[3] = __uint_as_float(r23 & 0xffff0000u) + b[3];
                     }
                     uint2 o;
-                    o.x = cvt_pk_bf16(v[0], v[1]); o.y = cvt_pk_bf16(v[2], v[3]);
+                    o.x = m1_cvt_pk_bf16(v[0], v[1]); o.y = m1_cvt_pk_bf16(v[2], v[3]);
                     *reinterpret_cast<uint2*>(dst) = o;
                     if (want_stats) {
                         const float r0 = __uint_as_float(o.x << 16), r1 = __uint_as_float(o.x & 0xffff0000u);
@@ -614,15 +576,7 @@ int m1_halo_conv(const MfmaP& mp, int OCpad, hipStream_t st) {
       if (lg) fprintf(stderr, "halo: nthr %d BN %d nchunks %d nxit %d stages %d TW %d TH %d %s\n", p.nthr, p.BNh, p.nchunks, nxit, p.stages, p.TW, p.TH, kern ? "static" : "runtime"); }
     if (!kern) kern = p.nthr == 512 ? (p.BNh == 32 ? conv_halo_kernel<2, 512, 0, 0> : conv_halo_kernel<1, 512, 0, 0>)
                                     : (p.BNh == 32 ? conv_halo_kernel<2, 256, 0, 0> : conv_halo_kernel<1, 256, 0, 0>);
-    {
-        static const void* done[24]; static int ndone = 0;
-        bool seen = false;
-        for (int q = 0; q < ndone; ++q) seen |= done[q] == (const void*)kern;
-        if (!seen) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-            if (ndone < 24) done[ndone++] = (const void*)kern;
-        }
-    }
+    if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel(p.ncls == 4 ? "conv_halo_cls:bn%d" : "conv_halo:bn%d", p.BNh);
     hipLaunchKernelGGL(kern, dim3(slices, nsplit), dim3(p.nthr), smem, st, p);
     return m1_check_launch();

@@ -2,9 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gather.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+#include "cdna4.h"
 
 #define MF_MAX_TAPS 27
 #define MF_MAX_CLASSES 8

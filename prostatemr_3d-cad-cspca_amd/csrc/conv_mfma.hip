@@ -21,8 +21,6 @@
 #include "conv_t3.h"
 #include <stdlib.h>
 
-__device__ __forceinline__ int swz(int row, int seg) { return seg ^ ((-(row >> 2)) & 3); }
-
 // n (< SEG) elements starting at p, zero padded to one 16-byte segment (element-wise loads: p need not be aligned)
 template <typename T>
 __device__ __forceinline__ uint4 load_partial_seg(const T* p, int n) {
@@ -34,32 +32,12 @@ __device__ __forceinline__ uint4 load_partial_seg(const T* p, int n) {
     return u.v;
 }
 
-// 64 zero bytes: the source of every LDS-DMA piece that falls outside the volume / beyond the K range
-__device__ __attribute__((aligned(64))) unsigned int m1_zero_page[16];
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-// one wave-instruction: 64 lanes x 16 bytes from per-lane global addresses to lds_wave_base + lane*16
-__device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
-
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4_t lds_read128(unsigned lds_addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-    return v;
-}
-// all outstanding LDS reads have landed; tying the fragment makes its consumers wait behind this statement
-__device__ __forceinline__ void lds_wait(u32x4_t& v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)); }
-// no instruction: only orders the consumers of v behind the preceding (volatile) wait
-__device__ __forceinline__ void lds_tie(u32x4_t& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(unsigned long long)(lptr_t)p; }
 
 // GLDS = true (every concat member a multiple of one 64-byte K-chunk): both operands go global -> LDS by LDS-DMA
 // (global_load_lds_dwordx4), no staging registers and no ds_write pass -- the VGPR -> LDS store path (<= 85 B/clk/CU)
 // was the bound of the register-staged loop.  The DMA writes lane-linear, so the XOR swizzle is applied on the SOURCE
-// side: the lane that owns LDS slot (row, s) fetches K-segment s ^ swz(row).
+// side: the lane that owns LDS slot (row, s) fetches K-segment s ^ m1_swz64(row).
 // KG > 1 (round 6, LDS-DMA path): K GROUPS inside the block instead of split-K across blocks for the deep levels' small launches
 // (M = 4,000 / 500 voxels per sample: a few hundred tiles).  The block carries KG wave groups of WM x WN waves; group g walks the g-th
 // K range of the tile with its own pipeline buffers, the groups' accumulators are added through LDS in group order, and group 0 runs
@@ -170,7 +148,6 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
     // register staging: logical segment tid&3, swizzled when written; LDS-DMA: slot tid&3, swizzled when fetched
     // (rows tid>>2 + (NTHR/4)*i and (tid + NTHR*i)>>2 all share (row>>2)&3 = (tid>>4)&3)
     const int lseg = GLDS ? ((tid & 3) ^ ((-(tid >> 4)) & 3)) : (tid & 3);
-    const unsigned char* zero_pg = reinterpret_cast<const unsigned char*>(m1_zero_page);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
     // incremental loader state (aligned case): current tap / concat member / channel offset and per-row bases
@@ -368,14 +345,14 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
 #pragma unroll
             for (int i = 0; i < A_LD; ++i) {
                 const int row = lrow + (NTHR / 4) * i;
-                *reinterpret_cast<uint4*>(A_s + (buf * KC + kc) * A_BYTES + row * 64 + swz(row, lseg) * 16) = ra[kc][i];
+                *reinterpret_cast<uint4*>(A_s + (buf * KC + kc) * A_BYTES + row * 64 + m1_swz64(row, lseg) * 16) = ra[kc][i];
             }
 #pragma unroll
             for (int i = 0; i < B_LD; ++i) {
                 const int e = tid + NTHR * i;
                 if (e < BN * 4) {
                     const int row = e >> 2;
-                    *reinterpret_cast<uint4*>(B_s + (buf * KC + kc) * B_BYTES + row * 64 + swz(row, e & 3) * 16) = rb[kc][i];
+                    *reinterpret_cast<uint4*>(B_s + (buf * KC + kc) * B_BYTES + row * 64 + m1_swz64(row, e & 3) * 16) = rb[kc][i];
                 }
             }
         }
@@ -383,8 +360,8 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
 
     const int fr = lane & 15, fs = lane >> 4;
     // fragment read addresses of tile (i or j) = base + 1024*tile (16 rows x 64 B; the swizzle term is tile-invariant)
-    const unsigned a_rd = lds_addr_of(A_s) + (wm * (BM / WM) + fr) * 64 + swz(fr, fs) * 16;
-    const unsigned b_rd = lds_addr_of(B_s) + (wn * (BN / WN) + fr) * 64 + swz(fr, fs) * 16;
+    const unsigned a_rd = lds_addr_of(A_s) + (wm * (BM / WM) + fr) * 64 + m1_swz64(fr, fs) * 16;
+    const unsigned b_rd = lds_addr_of(B_s) + (wn * (BN / WN) + fr) * 64 + m1_swz64(fr, fs) * 16;
     // (K groups share the block's barriers: every group runs the stages of a FULL range; beyond its own range a group stages zeros)
     const int nstages = KG > 1 ? (cps + KC - 1) / KC : (nchunks + KC - 1) / KC;
     if (nstages > 0) {
@@ -402,18 +379,18 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
             u32x4_t af[KC][TM], bfr[KC][TN];
             auto rd = [&](int kc) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) af[kc][i] = lds_read128(a_rd + (buf * KC + kc) * A_BYTES + i * 1024);
+                for (int i = 0; i < TM; ++i) af[kc][i] = m1_lds_read128(a_rd + (buf * KC + kc) * A_BYTES + i * 1024);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) bfr[kc][j] = lds_read128(b_rd + (buf * KC + kc) * B_BYTES + j * 1024);
+                for (int j = 0; j < TN; ++j) bfr[kc][j] = m1_lds_read128(b_rd + (buf * KC + kc) * B_BYTES + j * 1024);
             };
             rd(0);
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) {
-                lds_wait(af[kc][0]);                       // one s_waitcnt for the whole chunk, the other fragments are tied to it
+                m1_lds_wait(af[kc][0]);                       // one s_waitcnt for the whole chunk, the other fragments are tied to it
 #pragma unroll
-                for (int i = 1; i < TM; ++i) lds_tie(af[kc][i]);
+                for (int i = 1; i < TM; ++i) m1_lds_tie(af[kc][i]);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) lds_tie(bfr[kc][j]);
+                for (int j = 0; j < TN; ++j) m1_lds_tie(bfr[kc][j]);
                 if (kc + 1 < KC) rd(kc + 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -438,12 +415,12 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int row = wm * (BM / WM) + i * 16 + fr;
-                af[i] = *reinterpret_cast<const uint4*>(A_s + (buf * KC + kc) * A_BYTES + row * 64 + swz(row, fs) * 16);
+                af[i] = *reinterpret_cast<const uint4*>(A_s + (buf * KC + kc) * A_BYTES + row * 64 + m1_swz64(row, fs) * 16);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int row = wn * (BN / WN) + j * 16 + fr;
-                bfr[j] = *reinterpret_cast<const uint4*>(B_s + (buf * KC + kc) * B_BYTES + row * 64 + swz(row, fs) * 16);
+                bfr[j] = *reinterpret_cast<const uint4*>(B_s + (buf * KC + kc) * B_BYTES + row * 64 + m1_swz64(row, fs) * 16);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -961,12 +938,7 @@ static int launch_cfg_kc(const MfmaP& mp, long long maxM, int OCpad, hipStream_t
     dim3 grid((unsigned)(cdiv_ll(cdiv_ll(maxM, BM), 8) * 8), mp.nclasses * mp.ksplit, OCpad / BN);
     const size_t smem = mfma_smem_bytes<T, BM, BN, KC, WM * WN * 64>();
     auto kern = mp.aligned ? conv_mfma_kernel<T, BM, BN, WM, WN, KC, true> : conv_mfma_kernel<T, BM, BN, WM, WN, KC, false>;
-    static bool attr_set = false;     // per instantiation
-    if (smem > 48 * 1024 && !attr_set) {
-        if (hipFuncSetAttribute((const void*)conv_mfma_kernel<T, BM, BN, WM, WN, KC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return M1_ERR_LAUNCH;
-        if (hipFuncSetAttribute((const void*)conv_mfma_kernel<T, BM, BN, WM, WN, KC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return M1_ERR_LAUNCH;
-        attr_set = true;
-    }
+    if (smem > 48 * 1024 && m1_allow_dynamic_lds((const void*)kern, (int)smem) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("conv_mfma:%dx%d:w%d:ks%d", BM, BN, WM * WN, mp.ksplit);
     hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, st, mp);
     return m1_check_launch();
@@ -979,11 +951,7 @@ static int launch_cfg_kg(const MfmaP& mp, long long maxM, int OCpad, hipStream_t
     if constexpr (sizeof(T) != 2 || smem > 160 * 1024 - 256 || WM * WN * 64 * KG > 1024) return M1_ERR_UNSUPPORTED;
     else {
         dim3 grid((unsigned)(cdiv_ll(cdiv_ll(maxM, BM), 8) * 8), mp.nclasses * mp.ksplit, OCpad / BN);
-        static bool attr_set = false;     // per instantiation
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)conv_mfma_kernel<T, BM, BN, WM, WN, 2, true, KG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return M1_ERR_LAUNCH;
-            attr_set = true;
-        }
+        if (m1_allow_dynamic_lds((const void*)conv_mfma_kernel<T, BM, BN, WM, WN, 2, true, KG>, (int)smem) != M1_OK) return M1_ERR_LAUNCH;
         m1_note_kernel("conv_mfma:%dx%d:w%d:ks%d:kg%d", BM, BN, WM * WN, mp.ksplit, KG);
         hipLaunchKernelGGL((conv_mfma_kernel<T, BM, BN, WM, WN, 2, true, KG>), grid, dim3(WM * WN * 64 * KG), smem, st, mp);
         return m1_check_launch();

@@ -17,13 +17,6 @@
 #include "reduce.h"
 #include <stdlib.h>
 
-typedef unsigned u32x4p_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(2))) __bf16 pbf2_t;
-typedef __attribute__((ext_vector_type(2))) float pf2_t;
-__device__ __forceinline__ unsigned pw_cvt_pk(float a, float b) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((pf2_t){a, b}, pbf2_t));
-}
-__device__ __forceinline__ int pw_swz(int row, int seg) { return seg ^ ((-(row >> 2)) & 3); }
 
 struct PwP {
     MfmaP m;
@@ -48,7 +41,7 @@ __global__ void __launch_bounds__(256) conv_pw_kernel(PwP p) {
         for (int q = tid; q < NCH * BN * 4; q += 256) {
             const int ch = q / (BN * 4), r = (q / 4) % BN, s = q & 3;
             const uint4 v = *reinterpret_cast<const uint4*>(wp + (long long)(oc0 + r) * p.kpad + (ch * 4 + s) * 8);
-            *reinterpret_cast<uint4*>(smem + ((ch * BN + r) * 4 + pw_swz(r, s)) * 16) = v;
+            *reinterpret_cast<uint4*>(smem + ((ch * BN + r) * 4 + m1_swz64(r, s)) * 16) = v;
         }
     }
     __syncthreads();
@@ -79,7 +72,7 @@ __global__ void __launch_bounds__(256) conv_pw_kernel(PwP p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) bias_r[j][r] = (oc + r < m.OCn) ? m1_bias_at(m, oc + r) : 0.f;
     }
-    const unsigned char* const w_rd = smem + fr * 64 + pw_swz(fr, fs) * 16;     // fragment of oc row j*16 + fr: + (q*BN + j*16)*64
+    const unsigned char* const w_rd = smem + fr * 64 + m1_swz64(fr, fs) * 16;     // fragment of oc row j*16 + fr: + (q*BN + j*16)*64
 
     const bool want_stats = m.stat_partial != nullptr;
     // InstanceNorm-backward sums instead of statistics (MfmaP::ib_x: the output is d(a), a = lrelu(IN(x)); round 4)
@@ -119,15 +112,15 @@ __global__ void __launch_bounds__(256) conv_pw_kernel(PwP p) {
     const long long step = (long long)p.nwaves * 32;
     // voxel fragments: 16 bytes per lane and chunk, straight from the NDHWC rows; the next tile's are fetched before this
     // tile's MFMAs (the loop has no other latency hiding than the waves per SIMD)
-    u32x4p_t xf[2][NCH], xn[2][NCH];
-    auto fetch = [&](long long v0, u32x4p_t (&x)[2][NCH]) {
+    u32x4_t xf[2][NCH], xn[2][NCH];
+    auto fetch = [&](long long v0, u32x4_t (&x)[2][NCH]) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const long long v = v0 + i * 16 + fr;
 #pragma unroll
             for (int q = 0; q < NCH; ++q) {
-                x[i][q] = (u32x4p_t){0u, 0u, 0u, 0u};
-                if (v < p.Mtot && xp[q]) x[i][q] = *reinterpret_cast<const u32x4p_t*>(xp[q] + v * xC[q]);
+                x[i][q] = (u32x4_t){0u, 0u, 0u, 0u};
+                if (v < p.Mtot && xp[q]) x[i][q] = *reinterpret_cast<const u32x4_t*>(xp[q] + v * xC[q]);
             }
         }
     };
@@ -147,7 +140,7 @@ __global__ void __launch_bounds__(256) conv_pw_kernel(PwP p) {
         for (int q = 0; q < NCH; ++q)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const u32x4p_t wf = *reinterpret_cast<const u32x4p_t*>(w_rd + (q * BN + j * 16) * 64);
+                const u32x4_t wf = *reinterpret_cast<const u32x4_t*>(w_rd + (q * BN + j * 16) * 64);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)       // D[oc][voxel]: weights as A, voxels as B
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf), __builtin_bit_cast(bf16x8_t, xf[i][q]), acc[i][j], 0, 0, 0);
@@ -167,12 +160,12 @@ __global__ void __launch_bounds__(256) conv_pw_kernel(PwP p) {
                 if (o_fast[j]) {
                     if (o_acc[j]) {
                         const uint2 ov = *reinterpret_cast<const uint2*>(dst);
-                        const unsigned r01 = pw_cvt_pk(v[0], v[1]), r23 = pw_cvt_pk(v[2], v[3]);
+                        const unsigned r01 = m1_cvt_pk_bf16(v[0], v[1]), r23 = m1_cvt_pk_bf16(v[2], v[3]);
                         v[0] = __uint_as_float(r01 << 16) + __uint_as_float(ov.x << 16); v[1] = __uint_as_float(r01 & 0xffff0000u) + __uint_as_float(ov.x & 0xffff0000u);
                         v[2] = __uint_as_float(r23 << 16) + __uint_as_float(ov.y << 16); v[3] = __uint_as_float(r23 & 0xffff0000u) + __uint_as_float(ov.y & 0xffff0000u);
                     }
                     uint2 o;
-                    o.x = pw_cvt_pk(v[0], v[1]); o.y = pw_cvt_pk(v[2], v[3]);
+                    o.x = m1_cvt_pk_bf16(v[0], v[1]); o.y = m1_cvt_pk_bf16(v[2], v[3]);
                     *reinterpret_cast<uint2*>(dst) = o;
                     if (want_stats) {
                         const float r0 = __uint_as_float(o.x << 16), r1 = __uint_as_float(o.x & 0xffff0000u);
@@ -263,15 +256,7 @@ int m1_pw_conv(const MfmaP& mp, int OCpad, int BN, hipStream_t st) {
 #undef PK
     if (!kern) return M1_ERR_UNSUPPORTED;
     const size_t smem = (size_t)NCH * BN * 64;
-    if (smem > 48 * 1024) {
-        static const void* done[16]; static int ndone = 0;
-        bool seen = false;
-        for (int q = 0; q < ndone; ++q) seen |= done[q] == (const void*)kern;
-        if (!seen) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-            if (ndone < 16) done[ndone++] = (const void*)kern;
-        }
-    }
+    if (smem > 48 * 1024 && m1_allow_dynamic_lds((const void*)kern, 64 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("conv_pw:bn%d", BN);
     hipLaunchKernelGGL(kern, dim3(OCpad / BN, p.nwaves / 4), dim3(256), smem, st, p);
     return m1_check_launch();

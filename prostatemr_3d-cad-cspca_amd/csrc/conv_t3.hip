@@ -32,21 +32,11 @@
 #include "conv_t3.h"
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 #define CT3_BM 256
 #define CT3_THREADS 512
 #define CT3_NAS 2            // A-piece slots per wave in each of the two issue phases of a kd slice: 2 * 2 * 8 KB >= (256 + 2 W + 2) * 64 B
 
-__device__ __forceinline__ void ct3_dma(i32x4_t rs, unsigned lds, unsigned voff, unsigned soff) {
-    // (M0 is written here without a clobber: "m0" is a reserved register to hipcc -- it warns on the clobber -- and these kernels contain no
-    // compiler-generated M0 use that a stale value could reach; tools/isa_async_check.py / tests/test_build_props.py verify that on the ISA)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-template <int N> __device__ __forceinline__ void ct3_vmwait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 __device__ __forceinline__ u32x4_t ct3_lds(unsigned addr) {                 // ds_read_b128 at a 32-bit LDS address (compiler-visible)
     return *reinterpret_cast<const __attribute__((address_space(3))) u32x4_t*>((unsigned long long)addr);
 }
@@ -209,7 +199,7 @@ __global__ void __launch_bounds__(CT3_THREADS, 2) conv_t3_kernel(MfmaP p, Ct3P q
         for (int sl = 0; sl < CT3_NAS; ++sl) {
             const int g = a_vox[ph][sl] + vsh;                   // voxel of the sample (negative / beyond it: out of range -> zeros)
             const unsigned vo = (unsigned)(__mul24(g, Cs2) + cb + a_ssl[ph][sl]);
-            ct3_dma(rs, a_dst[ph][sl] == trash ? trash : a_dst[ph][sl] + (unsigned)(par * CT3_ASTRIDE), g < 0 ? OOB : vo, 0);
+            m1_lds_dma(rs, a_dst[ph][sl] == trash ? trash : a_dst[ph][sl] + (unsigned)(par * CT3_ASTRIDE), g < 0 ? OOB : vo, 0);
         }
     };
     // weights of interval qi into ring slot `slot`: taps (dd, dh, -1..1) of its chunk
@@ -220,7 +210,7 @@ __global__ void __launch_bounds__(CT3_THREADS, 2) conv_t3_kernel(MfmaP p, Ct3P q
         for (int sl = 0; sl < NBS; ++sl) {
             const int o = b_tap[sl] == 0 ? o0 : (b_tap[sl] == 1 ? o1 : (b_tap[sl] == 2 ? o2 : -1));
             i32x4_t rs = rs_b; rs.z = o >= 0 ? 0x7fffffff : 0;
-            ct3_dma(rs, b_dst[sl] == trash ? trash : b_dst[sl] + (unsigned)(slot * BSTAGE), b_vo[sl], o >= 0 ? (unsigned)o : 0u);
+            m1_lds_dma(rs, b_dst[sl] == trash ? trash : b_dst[sl] + (unsigned)(slot * BSTAGE), b_vo[sl], o >= 0 ? (unsigned)o : 0u);
         }
     };
 
@@ -286,8 +276,8 @@ __global__ void __launch_bounds__(CT3_THREADS, 2) conv_t3_kernel(MfmaP p, Ct3P q
                         const int qi = 3 * st + DHI;
                         // ring of 3: only the group issued one interval ago may be in flight; ring of 2: nothing (the weights of this
                         // interval were issued one interval ago)
-                        if constexpr (RING == 2) ct3_vmwait<0>();
-                        else if constexpr (DHI == 0) ct3_vmwait<NBS>(); else ct3_vmwait<NBS + CT3_NAS>();
+                        if constexpr (RING == 2) m1_wait_vm_imm<0>();
+                        else if constexpr (DHI == 0) m1_wait_vm_imm<NBS>(); else m1_wait_vm_imm<NBS + CT3_NAS>();
                         __builtin_amdgcn_s_barrier();
                         compute(parc, dhc, [&]() {
                             if constexpr (RING == 3) issue_b(qi + 2, (DHI + 2) % 3); else issue_b(qi + 1, (PAR + DHI + 1) & 1);
@@ -297,7 +287,7 @@ __global__ void __launch_bounds__(CT3_THREADS, 2) conv_t3_kernel(MfmaP p, Ct3P q
                 }
             });
         }
-        ct3_vmwait<0>();
+        m1_wait_vm_imm<0>();
     }
     __syncthreads();
 
@@ -462,15 +452,7 @@ int m1_ct3_conv(const MfmaP& mp, int BN, int OCpad, hipStream_t st) {
     if (mp.cls_ntaps[0] != 27 && mp.cls_ntaps[0] != 9) return M1_ERR_UNSUPPORTED;
     const size_t smem = ct3_smem(BN, q.smax);
     void (*kern)(MfmaP, Ct3P) = BN == 128 ? conv_t3_kernel<2, 2> : (BN == 160 ? conv_t3_kernel<3, 2> : (BN == 192 ? conv_t3_kernel<3, 3> : conv_t3_kernel<4, 4>));
-    {
-        static const void* done[4]; static int ndone = 0;
-        bool seen = false;
-        for (int i = 0; i < ndone; ++i) seen |= done[i] == (const void*)kern;
-        if (!seen) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-            if (ndone < 4) done[ndone++] = (const void*)kern;
-        }
-    }
+    if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     const long long tiles = (long long)q.tps * mp.N;
     dim3 grid((unsigned)(cdiv_ll(tiles, 8) * 8), (unsigned)mp.ksplit, (unsigned)(OCpad / BN));
     m1_note_kernel("conv_t3:bn%d:ks%d", BN, mp.ksplit);

@@ -59,11 +59,7 @@ __global__ void __launch_bounds__(256) m1_scribble_kernel(int spins) {
 }
 
 extern "C" int m1_debug_scribble(int blocks, int spins, void* stream) {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)m1_scribble_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-        attr = true;
-    }
+    if (m1_allow_dynamic_lds((const void*)m1_scribble_kernel, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     if (blocks <= 0) blocks = 512;
     hipLaunchKernelGGL(m1_scribble_kernel, dim3(blocks), dim3(256), 160 * 1024, (hipStream_t)stream, spins < 0 ? 0 : spins);
     return m1_check_launch();

@@ -9,10 +9,9 @@
 // One block = one (tap, a-tile, b-tile, voxel-split); partial results are combined with fp32 atomics in L2.
 #include "common.h"
 #include "gather.h"
+#include "cdna4.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 template <typename T> struct WT;
 template <> struct WT<bf16_t> { static constexpr int SEG = 8; };

@@ -29,13 +29,9 @@
 // wgrad_t3s.hip holds the fp32 kernels for layers with few channels and for pointwise layers.
 #include "common.h"
 #include "gather.h"
+#include "cdna4.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 #define T3_WAVES 12
 #define T3_THREADS (T3_WAVES * 64)
@@ -52,21 +48,8 @@ struct T3P {
     int want_bsum;
 };
 
-// transpose read, compiler-visible (it packs the two halves of a fragment into one register quadruple, folds constant
-// offsets into the instruction and schedules the lgkmcnt waits).  The LDS-DMA below is issued from inline asm, so the compiler
-// never sees a pending LDS write that it would drain with vmcnt(0) in front of every read.
-__device__ __forceinline__ s16x4_t t3_tr(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p);
-}
 __device__ __forceinline__ bf16x8_t t3_frag(s16x4_t lo, s16x4_t hi) {
     return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-// 64 lanes x 16 bytes, global (buffer resource `rs`, per-lane byte offset `voff`; out of range -> zeros) -> LDS at the
-// wave-uniform byte address `lds` + 16 * lane.  M0 carries the LDS base of an LDS-DMA.
-__device__ __forceinline__ void t3_dma(i32x4_t rs, unsigned lds, unsigned voff) {
-    // (M0 is written here without a clobber: "m0" is a reserved register to hipcc -- it warns on the clobber -- and these kernels contain no
-    // compiler-generated M0 use that a stale value could reach; tools/isa_async_check.py / tests/test_build_props.py verify that on the ISA)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(lds), "v"(voff), "s"(rs) : "memory");
 }
 // at most P * (S - 2) LDS-DMA pieces of this wave still in flight (every wave issues P pieces per stage)
 template <int P> __device__ __forceinline__ void t3_wait_stages(int S) {
@@ -215,9 +198,9 @@ __global__ void __launch_bounds__(T3_THREADS, 3) wgrad_t3_kernel(T3P p) {
                 const unsigned hh = (unsigned)(pk[it] & 0xff), ww = (unsigned)(pk[it] >> 8);
                 unsigned o = (hh + (unsigned)ah0) < (unsigned)p.AH ? vo[it] : OOB;
                 o = (ww + (unsigned)aw0) < (unsigned)p.AW ? o : OOB;
-                t3_dma((!BIGB && second[it]) ? ra1 : ra0, d, o);
+                m1_lds_dma((!BIGB && second[it]) ? ra1 : ra0, d, o);
             } else {
-                t3_dma(rb, d, (unsigned)(pk[it] + bh0) < (unsigned)p.BH ? vo[it] : OOB);
+                m1_lds_dma(rb, d, (unsigned)(pk[it] + bh0) < (unsigned)p.BH ? vo[it] : OOB);
             }
         }
     };
@@ -294,24 +277,24 @@ __global__ void __launch_bounds__(T3_THREADS, 3) wgrad_t3_kernel(T3P p) {
         for (int ks = 0; ks < 4; ++ks) {
             bf16x8_t bf0, bf1, af0, af1, af2;
             const int bo0 = ks * 16 * 128, bo1 = bo0 + 4 * 128;
-            bf0 = t3_frag(t3_tr(b0p + bo0), t3_tr(b0p + bo1));
-            bf1 = t3_frag(t3_tr(b1p + bo0), t3_tr(b1p + bo1));
+            bf0 = t3_frag(m1_tr_read(b0p + bo0), m1_tr_read(b0p + bo1));
+            bf1 = t3_frag(m1_tr_read(b1p + bo0), m1_tr_read(b1p + bo1));
             if (KWS) {
                 constexpr int AW_ = KWS + 2;
                 const int th_c = KWS == 8 ? 2 * ks : (KWS == 16 ? ks : ks >> 1), tw_c = KWS == 32 ? 16 * (ks & 1) : 0;
                 const int ao0 = (th_c * AW_ + tw_c) * 128, ao1 = ao0 + 4 * 128;
-                af0 = t3_frag(t3_tr(a0p + ao0), t3_tr(a0p + ao1));
-                af1 = t3_frag(t3_tr(a1p + ao0), t3_tr(a1p + ao1));
-                af2 = t3_frag(t3_tr(a2p + ao0), t3_tr(a2p + ao1));
+                af0 = t3_frag(m1_tr_read(a0p + ao0), m1_tr_read(a0p + ao1));
+                af1 = t3_frag(m1_tr_read(a1p + ao0), m1_tr_read(a1p + ao1));
+                af2 = t3_frag(m1_tr_read(a2p + ao0), m1_tr_read(a2p + ao1));
             } else {
                 const unsigned char* s0 = At + sb;
                 unsigned aA = a_tab[KWS ? 0 : ks][0], aB = a_tab[KWS ? 0 : ks][1];
                 asm volatile("" : "+v"(aA), "+v"(aB));       // (keeps the 16 derived tap addresses out of loop-invariant registers)
-                af0 = t3_frag(t3_tr(s0 + aA), t3_tr(s0 + aB));
-                if (STR == 1) af1 = t3_frag(t3_tr(s0 + ((aA + 128u) ^ m1)), t3_tr(s0 + ((aB + 128u) ^ m1)));
-                else af1 = t3_frag(t3_tr(s0 + aA + (unsigned)(PLANE * 128)), t3_tr(s0 + aB + (unsigned)(PLANE * 128)));   // the odd-column plane, same row
-                if (STR == 1) af2 = t3_frag(t3_tr(s0 + ((aA + 256u) ^ 64u)), t3_tr(s0 + ((aB + 256u) ^ 64u)));
-                else af2 = t3_frag(t3_tr(s0 + ((aA + 128u) ^ m1)), t3_tr(s0 + ((aB + 128u) ^ m1)));                     // the even plane, next column
+                af0 = t3_frag(m1_tr_read(s0 + aA), m1_tr_read(s0 + aB));
+                if (STR == 1) af1 = t3_frag(m1_tr_read(s0 + ((aA + 128u) ^ m1)), m1_tr_read(s0 + ((aB + 128u) ^ m1)));
+                else af1 = t3_frag(m1_tr_read(s0 + aA + (unsigned)(PLANE * 128)), m1_tr_read(s0 + aB + (unsigned)(PLANE * 128)));   // the odd-column plane, same row
+                if (STR == 1) af2 = t3_frag(m1_tr_read(s0 + ((aA + 256u) ^ 64u)), m1_tr_read(s0 + ((aB + 256u) ^ 64u)));
+                else af2 = t3_frag(m1_tr_read(s0 + ((aA + 128u) ^ m1)), m1_tr_read(s0 + ((aB + 128u) ^ m1)));                     // the even plane, next column
             }
             if (do_bsum) { accb0 += t3_sum8(bf0); accb1 += t3_sum8(bf1); }
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af0, bf0, acc[0][0], 0, 0, 0);
@@ -458,9 +441,9 @@ __global__ void __launch_bounds__(T3_THREADS, 3) wgrad_t3f_kernel(T3P p) {
                 const unsigned hh = (unsigned)(pk[it] & 0xff), ww = (unsigned)(pk[it] >> 8);
                 unsigned o = (hh + (unsigned)ah0) < (unsigned)p.AH ? vo[it] : OOB;
                 o = (ww + (unsigned)aw0) < (unsigned)p.AW ? o : OOB;
-                t3_dma((!BIGB && second[it]) ? ra1 : ra0, d, o);
+                m1_lds_dma((!BIGB && second[it]) ? ra1 : ra0, d, o);
             } else {
-                t3_dma(rb, d, (unsigned)(pk[it] + bh0) < (unsigned)p.BH ? vo[it] : OOB);
+                m1_lds_dma(rb, d, (unsigned)(pk[it] + bh0) < (unsigned)p.BH ? vo[it] : OOB);
             }
         }
     };
@@ -625,15 +608,7 @@ int m1_t3_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st, int nm
     else if (s2) kern = p.KWs == 8 ? wgrad_t3_kernel<8, true, 2> : (p.KWs == 16 ? wgrad_t3_kernel<16, true, 2> : (p.KWs == 32 ? wgrad_t3_kernel<32, true, 2> : wgrad_t3_kernel<0, true, 2>));
     else if (bigb) kern = p.KWs == 8 ? wgrad_t3_kernel<8, true, 1> : (p.KWs == 16 ? wgrad_t3_kernel<16, true, 1> : (p.KWs == 32 ? wgrad_t3_kernel<32, true, 1> : wgrad_t3_kernel<0, true, 1>));
     else kern = p.KWs == 8 ? wgrad_t3_kernel<8, false, 1> : (p.KWs == 16 ? wgrad_t3_kernel<16, false, 1> : (p.KWs == 32 ? wgrad_t3_kernel<32, false, 1> : wgrad_t3_kernel<0, false, 1>));
-    {
-        static const void* done[20]; static int ndone = 0;
-        bool seen = false;
-        for (int q = 0; q < ndone; ++q) seen |= done[q] == (const void*)kern;
-        if (!seen) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-            if (ndone < 20) done[ndone++] = (const void*)kern;
-        }
-    }
+    if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel(f32 ? "wgrad_t3f:kws%d:big%d" : (s2 ? "wgrad_t3:s2:kws%d:big%d" : "wgrad_t3:kws%d:big%d"), p.KWs, (int)bigb);
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)nsplit, (unsigned)(gzu * g.kd)), dim3(T3_THREADS), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;

@@ -14,17 +14,14 @@
 // * tile table, fixed DMA piece slots, per-split partial copies + fixed-order fold as in wgrad_t3.hip (no float atomics).
 #include "common.h"
 #include "gather.h"
+#include "cdna4.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4s_t;
 template <int TL> struct TsAcc;
 template <> struct TsAcc<32> { typedef f32x16_t type; static constexpr int NE = 16, VG = 2;
     static __device__ __forceinline__ type mfma(float a, float b, type c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); } };
-template <> struct TsAcc<16> { typedef f32x4s_t type; static constexpr int NE = 4, VG = 4;
+template <> struct TsAcc<16> { typedef f32x4_t type; static constexpr int NE = 4, VG = 4;
     static __device__ __forceinline__ type mfma(float a, float b, type c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); } };
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 #define TS_WAVES 12
 #define TS_THREADS (TS_WAVES * 64)
@@ -39,11 +36,6 @@ struct TSP {
     int want_bsum;
 };
 
-__device__ __forceinline__ void ts_dma(i32x4_t rs, unsigned lds, unsigned voff) {
-    // (M0 is written here without a clobber: "m0" is a reserved register to hipcc -- it warns on the clobber -- and these kernels contain no
-    // compiler-generated M0 use that a stale value could reach; tools/isa_async_check.py / tests/test_build_props.py verify that on the ISA)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(lds), "v"(voff), "s"(rs) : "memory");
-}
 
 // STR = stride of the gather in H and W (1, or 2: strided convs and, with the roles of the two sides swapped, transposed convs;
 // TF-SAME pad_before 0).  No de-interleaving as in the bf16 kernel: a dword fragment read is conflict-free whatever the rows.
@@ -137,9 +129,9 @@ __global__ void __launch_bounds__(TS_THREADS, 3) wgrad_t3s_kernel(TSP p) {
                 const unsigned hh = (unsigned)(pk[it] & 0xff), ww = (unsigned)(pk[it] >> 8);
                 unsigned o = (hh + (unsigned)ah0) < (unsigned)p.AH ? vo[it] : OOB;
                 o = (ww + (unsigned)aw0) < (unsigned)p.AW ? o : OOB;
-                ts_dma(ra, d, o);
+                m1_lds_dma(ra, d, o);
             } else {
-                ts_dma(rb, d, (unsigned)(pk[it] + bh0) < (unsigned)p.BH ? vo[it] : OOB);
+                m1_lds_dma(rb, d, (unsigned)(pk[it] + bh0) < (unsigned)p.BH ? vo[it] : OOB);
             }
         }
     };
@@ -294,15 +286,7 @@ int m1_t3s_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
 #define TSK(K_, S_) (TLh == 32 ? wgrad_t3s_kernel<K_, S_, 32> : wgrad_t3s_kernel<K_, S_, 16>)
     kern = s2 ? (kws == 32 ? TSK(32, 2) : (kws == 16 ? TSK(16, 2) : TSK(8, 2))) : (kws == 32 ? TSK(32, 1) : (kws == 16 ? TSK(16, 1) : TSK(8, 1)));
 #undef TSK
-    {
-        static const void* done[16]; static int ndone = 0;
-        bool seen = false;
-        for (int q = 0; q < ndone; ++q) seen |= done[q] == (const void*)kern;
-        if (!seen) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-            if (ndone < 16) done[ndone++] = (const void*)kern;
-        }
-    }
+    if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_t3s");
     hipLaunchKernelGGL(kern, dim3((unsigned)nbu, (unsigned)nsplit, (unsigned)(p.nau * g.kd)), dim3(TS_THREADS), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;
@@ -350,9 +334,9 @@ __global__ void __launch_bounds__(PW_THREADS, 2) wgrad_pwf_kernel(PWP p) {
         rb.z = __builtin_amdgcn_readfirstlane((int)(left * p.CB * 4)); rb.w = 0x00020000;
         const unsigned S0 = lds0 + (unsigned)(st * stage_bytes);
 #pragma unroll
-        for (int it = 0; it < ITS; ++it) ts_dma(ra, S0 + (unsigned)((wave + PW_WAVES * it) * 1024), voA[it]);
+        for (int it = 0; it < ITS; ++it) m1_lds_dma(ra, S0 + (unsigned)((wave + PW_WAVES * it) * 1024), voA[it]);
 #pragma unroll
-        for (int it = 0; it < ITS; ++it) ts_dma(rb, S0 + (unsigned)((nT + wave + PW_WAVES * it) * 1024), voB[it]);
+        for (int it = 0; it < ITS; ++it) m1_lds_dma(rb, S0 + (unsigned)((nT + wave + PW_WAVES * it) * 1024), voB[it]);
     };
     const int g = lane >> 5, c = lane & 31;
     const unsigned char* const aL = smem + ((32 * vq + g) * 64 + ah * 32 + c) * 4;
@@ -455,11 +439,7 @@ int m1_pwf_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     if (nsplit < 1) nsplit = 1;
     p.nsplit = (int)nsplit; p.Rx = g.rx; p.rx_stride = stride; p.rx_bias = nloc; p.want_bsum = g.bsum != nullptr;
     const size_t smem = 2 * (size_t)(2 * (PW_KT / 4) * 1024);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)wgrad_pwf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-        attr = true;
-    }
+    if (m1_allow_dynamic_lds((const void*)wgrad_pwf_kernel, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_pwf");
     hipLaunchKernelGGL(wgrad_pwf_kernel, dim3((unsigned)nbu, (unsigned)nsplit, (unsigned)nau), dim3(PW_THREADS), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;

@@ -15,37 +15,9 @@
 // * Few voxel splits per (tap, tile) (~2 blocks per CU in total): float atomics into R.
 #include "common.h"
 #include "gather.h"
+#include "cdna4.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(64))) unsigned int m1_zero_page_t[16];
-
-__device__ __forceinline__ void glds16t(const void* g, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ u32x2_t tr_read_t(unsigned lds_addr) {
-    u32x2_t v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_wait_t(u32x2_t& a, u32x2_t& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ bf16x8_t frag8t(u32x2_t lo, u32x2_t hi) {
-    return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3));
-}
-__device__ __forceinline__ void wait_vmt(int n) {
-    switch (n) {
-#define TW_(N_) case N_: asm volatile("s_waitcnt vmcnt(" #N_ ")" ::: "memory"); break;
-        TW_(0) TW_(1) TW_(2) TW_(3) TW_(4) TW_(5) TW_(6) TW_(7) TW_(8) TW_(9) TW_(10) TW_(11) TW_(12) TW_(13) TW_(14) TW_(15) TW_(16)
-        TW_(17) TW_(18) TW_(19) TW_(20) TW_(21) TW_(22) TW_(23) TW_(24)
-#undef TW_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
 // XOR applied to the 32-byte piece index of row kk (np = pieces per row, a power of two <= 8)
 __device__ __forceinline__ int piece_swz(int kk, int np) {
     return np == 8 ? ((kk & 3) | (((kk >> 3) & 1) << 2)) : (np == 4 ? (((kk >> 1) & 1) | (((kk >> 3) & 1) << 1)) : (np == 2 ? ((kk >> 3) & 1) : 0));
@@ -85,7 +57,6 @@ __global__ void __launch_bounds__(256) wgrad_tap_kernel(TapP p) {
     const int a0 = (bx / p.bTiles) * TA, b0 = (bx % p.bTiles) * TB;
     const int tap = bz;
     const int tkw = tap % p.kw, tkh = (tap / p.kw) % p.kh, tkd = tap / (p.kw * p.kh);
-    const unsigned char* zero_pg = reinterpret_cast<const unsigned char*>(m1_zero_page_t);
 
     // ---- per-lane DMA pieces: LDS slot q -> (row kk = voxel of the tile, physical slot); tile invariant ----
     // (buffer loads: the tile origin goes into the resource base, the lane keeps a constant 32-bit byte offset; an offset
@@ -186,7 +157,7 @@ __global__ void __launch_bounds__(256) wgrad_tap_kernel(TapP p) {
     for (int s = 0; s < S - 1; ++s) issue(s);
     int st = 0;
     for (int kt = by; kt < p.ntiles; kt += p.nsplit) {
-        wait_vmt(npiece * (S - 2));
+        m1_wait_vm<24>(npiece * (S - 2));
         __builtin_amdgcn_s_barrier();
         int stn = st + S - 1; if (stn >= S) stn -= S;
         issue(stn);
@@ -194,29 +165,29 @@ __global__ void __launch_bounds__(256) wgrad_tap_kernel(TapP p) {
         u32x2_t al[2][SUBA], ah[2][SUBA], bl[2][SUBB], bh[2][SUBB];
         auto rd = [&](int ks) {
 #pragma unroll
-            for (int x = 0; x < SUBA; ++x) { al[ks][x] = tr_read_t((a_ad[ks][0] + sb) ^ (x * 32)); ah[ks][x] = tr_read_t((a_ad[ks][1] + sb) ^ (x * 32)); }
+            for (int x = 0; x < SUBA; ++x) { al[ks][x] = m1_tr_read_asm((a_ad[ks][0] + sb) ^ (x * 32)); ah[ks][x] = m1_tr_read_asm((a_ad[ks][1] + sb) ^ (x * 32)); }
 #pragma unroll
-            for (int y = 0; y < SUBB; ++y) { bl[ks][y] = tr_read_t((b_ad[ks][0] + sb) ^ (y * 32)); bh[ks][y] = tr_read_t((b_ad[ks][1] + sb) ^ (y * 32)); }
+            for (int y = 0; y < SUBB; ++y) { bl[ks][y] = m1_tr_read_asm((b_ad[ks][0] + sb) ^ (y * 32)); bh[ks][y] = m1_tr_read_asm((b_ad[ks][1] + sb) ^ (y * 32)); }
         };
         rd(0);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-            for (int x = 0; x < SUBA; ++x) lds_wait_t(al[ks][x], ah[ks][x]);
+            for (int x = 0; x < SUBA; ++x) m1_lds_wait(al[ks][x], ah[ks][x]);
 #pragma unroll
-            for (int y = 0; y < SUBB; ++y) lds_wait_t(bl[ks][y], bh[ks][y]);
+            for (int y = 0; y < SUBB; ++y) m1_lds_wait(bl[ks][y], bh[ks][y]);
             if (ks == 0) rd(1);
             __builtin_amdgcn_sched_barrier(0);
             bf16x8_t bf[SUBB];
 #pragma unroll
-            for (int y = 0; y < SUBB; ++y) bf[y] = frag8t(bl[ks][y], bh[ks][y]);
+            for (int y = 0; y < SUBB; ++y) bf[y] = m1_frag8(bl[ks][y], bh[ks][y]);
             if (do_bsum) {
 #pragma unroll
                 for (int y = 0; y < SUBB; ++y) accb[y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bf[y], accb[y], 0, 0, 0);
             }
 #pragma unroll
             for (int x = 0; x < SUBA; ++x) {
-                const bf16x8_t af = frag8t(al[ks][x], ah[ks][x]);
+                const bf16x8_t af = m1_frag8(al[ks][x], ah[ks][x]);
 #pragma unroll
                 for (int y = 0; y < SUBB; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[y], acc[x][y], 0, 0, 0);
             }
@@ -297,15 +268,7 @@ int m1_tap_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     else if (TA == 128 && TB == 64) kern = wgrad_tap_kernel<4, 2>;
     else if (TA == 64 && TB == 128) kern = wgrad_tap_kernel<2, 4>;
     else kern = wgrad_tap_kernel<2, 2>;
-    {
-        static const void* done[4]; static int ndone = 0;
-        bool seen = false;
-        for (int q = 0; q < ndone; ++q) seen |= done[q] == (const void*)kern;
-        if (!seen) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-            if (ndone < 4) done[ndone++] = (const void*)kern;
-        }
-    }
+    if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     // partial copies + fixed-order fold instead of atomics (compact per-member copies, see wgrad_mfma.hip): bit-reproducible
     // weight gradients; M1_WG_DET=0 restores the atomic path
     int det = M1_CFG("M1_WG_DET", 1);

@@ -18,23 +18,8 @@
 //   order -- no floating-point atomics.  The equal-width members of a concat share one launch (blockIdx.z = member).
 #include "common.h"
 #include "gather.h"
+#include "cdna4.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(64))) unsigned int m1_zero_page_w[16];
-
-__device__ __forceinline__ void glds16w(const void* g, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
-// 4 voxels x 16 channels block -> this lane's channel, 4 consecutive voxels (see header)
-__device__ __forceinline__ s16x4_t tr_read(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p);
-}
 
 #define TF_MAX_NKS 4        // k-steps (of 32 voxels) per K-tile: 2, or 4 for the <= 16-channel layers (see tf_plan)
 #define TF_MAX_AIT 10       // LDS-DMA pieces per thread for the A tile
@@ -60,31 +45,6 @@ struct TfP {
     int nmem; const bf16_t* Am[M1_MAX_SRC]; long long rx_mem;
 };
 
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-// transpose-read by inline asm: hipcc cannot tell an LDS-DMA still in flight from the buffer being read and would wait
-// vmcnt(0) in front of every compiler-visible LDS read (no prefetch depth at all)
-__device__ __forceinline__ u32x2_t tr_read_asm(unsigned lds_addr) {
-    u32x2_t v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_wait2(u32x2_t& a, u32x2_t& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ bf16x8_t frag8(u32x2_t lo, u32x2_t hi) {
-    return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3));
-}
-// at most n LDS-DMA pieces of this wave still in flight (n wave-uniform)
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-#define TF_W(N_) case N_: asm volatile("s_waitcnt vmcnt(" #N_ ")" ::: "memory"); break;
-        TF_W(0) TF_W(1) TF_W(2) TF_W(3) TF_W(4) TF_W(5) TF_W(6) TF_W(7) TF_W(8) TF_W(9) TF_W(10) TF_W(11) TF_W(12)
-        TF_W(13) TF_W(14) TF_W(15) TF_W(16) TF_W(17) TF_W(18) TF_W(19) TF_W(20) TF_W(21) TF_W(22) TF_W(23) TF_W(24)
-        TF_W(25) TF_W(26) TF_W(27) TF_W(28) TF_W(29) TF_W(30) TF_W(31) TF_W(32) TF_W(33) TF_W(34) TF_W(35) TF_W(36)
-        TF_W(37) TF_W(38) TF_W(39) TF_W(40) TF_W(41) TF_W(42) TF_W(43) TF_W(44) TF_W(45) TF_W(46) TF_W(47) TF_W(48)
-#undef TF_W
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
 #define TF_MAX_STAGES 8
 
 template <int KD, int KH, int KW, int KPARTS, int TF_NKS>
@@ -109,7 +69,6 @@ __global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
     }
     const int PA = p.spra * 16, PB = p.sprb * 16;            // LDS row pitch (bytes)
     const int stage_bytes = p.a_bytes + p.b_bytes;           // [A tile][B tile] per stage
-    const unsigned char* zero_pg = reinterpret_cast<const unsigned char*>(m1_zero_page_w);
 
     // ---- per-lane description of its LDS-DMA pieces (the same for every K-tile).  Every wave issues nait + 1 pieces
     //      per stage (tiles padded to whole 256-slot rounds, padding fetches the zero page): static vmcnt arithmetic ----
@@ -222,7 +181,7 @@ __global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
     for (int s = 0; s < S - 1; ++s) issue(s);
     int st = 0;
     for (long long kt = kt0; kt < p.ntiles; kt += step) {
-        wait_vm(npiece * (S - 2));                     // this wave's pieces of tile kt have landed ...
+        m1_wait_vm<48>(npiece * (S - 2));             // this wave's pieces of tile kt have landed ...
         __builtin_amdgcn_s_barrier();                          // ... and everybody's; everybody is also done with tile kt - step
         int stn = st + S - 1; if (stn >= S) stn -= S;
         issue(stn);                                            // refill the buffer tile kt - step was read from
@@ -232,15 +191,15 @@ __global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
         u32x2_t bl[2], bh[2], al[2][CH], ah[2][CH];
         auto rd_unit = [&](int u, int set) {
             const int ks = u / KD, kd = u % KD;
-            if (kd == 0) { bl[ks & 1] = tr_read_asm(b_ad[ks][0] + sb); bh[ks & 1] = tr_read_asm(b_ad[ks][1] + sb); }
+            if (kd == 0) { bl[ks & 1] = m1_tr_read_asm(b_ad[ks][0] + sb); bh[ks & 1] = m1_tr_read_asm(b_ad[ks][1] + sb); }
 #pragma unroll
             for (int kh = 0; kh < KH; ++kh) {
                 const unsigned ro = sb + (unsigned)((kd * p.AHt + kh) * grp_pitch);
 #pragma unroll
                 for (int kw = 0; kw < KW; ++kw) {
                     if (((kd * CH + kh * KW + kw) % kparts) == part) {
-                        al[set][kh * KW + kw] = tr_read_asm(a_ad[ks][0][kw] + ro);
-                        ah[set][kh * KW + kw] = tr_read_asm(a_ad[ks][1][kw] + ro);
+                        al[set][kh * KW + kw] = m1_tr_read_asm(a_ad[ks][0][kw] + ro);
+                        ah[set][kh * KW + kw] = m1_tr_read_asm(a_ad[ks][1][kw] + ro);
                     }
                 }
             }
@@ -249,17 +208,17 @@ __global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const int ks = u / KD, kd = u % KD, set = u & 1;
-            if (kd == 0) lds_wait2(bl[ks & 1], bh[ks & 1]);
+            if (kd == 0) m1_lds_wait(bl[ks & 1], bh[ks & 1]);
 #pragma unroll
-            for (int c = 0; c < CH; ++c) lds_wait2(al[set][c], ah[set][c]);
+            for (int c = 0; c < CH; ++c) m1_lds_wait(al[set][c], ah[set][c]);
             if (u + 1 < NU) rd_unit(u + 1, set ^ 1);
             __builtin_amdgcn_sched_barrier(0);
-            const bf16x8_t bfr = frag8(bl[ks & 1], bh[ks & 1]);
+            const bf16x8_t bfr = m1_frag8(bl[ks & 1], bh[ks & 1]);
             if (do_bsum && kd == 0) accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bfr, accb, 0, 0, 0);
 #pragma unroll
             for (int c = 0; c < CH; ++c)
                 if (((kd * CH + c) % kparts) == part)
-                    acc[kd * CH + c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag8(al[set][c], ah[set][c]), bfr, acc[kd * CH + c], 0, 0, 0);
+                    acc[kd * CH + c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(m1_frag8(al[set][c], ah[set][c]), bfr, acc[kd * CH + c], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (++st == S) st = 0;
@@ -581,15 +540,7 @@ static int tf_wgrad_launch(const WgradSpec& g, long long nw, int nb, hipStream_t
     if (p.nks == 4 && g.kd == 1 && kparts == 1) kern = wgrad_tf_kernel<1, 3, 3, 1, 4>;
     if (p.nks == 4 && g.kd == 1 && kparts == 2) kern = wgrad_tf_kernel<1, 3, 3, 2, 4>;
     if (!kern) return M1_ERR_UNSUPPORTED;
-    {   // raise the dynamic-LDS limit once per instantiation
-        static const void* done[8]; static int ndone = 0;
-        bool seen = false;
-        for (int q = 0; q < ndone; ++q) seen |= done[q] == (const void*)kern;
-        if (!seen) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return M1_ERR_LAUNCH;
-            if (ndone < 8) done[ndone++] = (const void*)kern;
-        }
-    }
+    if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_tf");
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;

@@ -45,13 +45,37 @@ def test_library_creates_no_memset_nodes():
     assert len(hits) == 1 and hits[0][0] == "dispatch.hip" and "M1_MEMSET_KERNEL" in open(os.path.join(CSRC, "dispatch.hip")).read(), hits
 
 
+def _code_lines(path):
+    """(line number, text in front of any // comment) of a source file"""
+    return [(no, line.split("//")[0]) for no, line in enumerate(open(path), 1)]
+
+
+def test_cdna4_primitives_are_defined_once():
+    """The gfx950 primitives (LDS-DMA, transpose reads, the M0 write) are written once, in csrc/cdna4.h, and the dynamic-LDS opt-in
+    once, in m1_allow_dynamic_lds (config.hip): a copy in a kernel source would escape the comment that explains it and, for the M0
+    write, the list of sources the async check below derives from the helper's name."""
+    import glob
+    files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")))
+    for text in ("__builtin_amdgcn_global_load_lds", "ds_read_b64_tr_b16", "__builtin_amdgcn_ds_read_tr16_b64", "s_mov_b32 m0",
+                 "buffer_load_dwordx4"):
+        where = sorted({os.path.basename(f) for f in files for _, code in _code_lines(f) if text in code})
+        assert where == ["cdna4.h"], (text, where)
+    where = [os.path.basename(f) for f in files for _, code in _code_lines(f) if "hipFuncSetAttribute(" in code]
+    assert where == ["config.hip"], where
+    cfg = open(os.path.join(CSRC, "config.hip")).read()
+    body = cfg[cfg.index("int m1_allow_dynamic_lds("):]
+    assert "hipFuncSetAttribute(" in body[:body.index("\n}\n")]
+
+
 def _async_checked_sources():
     """The kernels whose inline asm issues loads the compiler's waitcnt pass cannot see, plus EVERY source whose inline asm writes M0
-    (the LDS-DMA helpers: `s_mov_b32 m0`) -- derived from the sources, so a new LDS-DMA kernel cannot stay outside the check
+    (it calls cdna4.h's buffer LDS-DMA helper m1_lds_dma, the one place with `s_mov_b32 m0`: test_cdna4_primitives_are_defined_once)
+    -- derived from the sources, so a new LDS-DMA kernel cannot stay outside the check
     (round-5 advisor: wgrad_t3s.hip, with two LDS-DMA kernels, was never listed)."""
     import glob
     base = ["conv_mfma.hip", "conv_t3.hip", "wgrad_tf.hip", "wgrad_t3.hip"]
-    m0 = [os.path.basename(f) for f in sorted(glob.glob(os.path.join(CSRC, "*.hip"))) if "s_mov_b32 m0" in open(f).read()]
+    m0 = [os.path.basename(f) for f in sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+          if any(re.search(r"\bm1_lds_dma\s*\(", code) for _, code in _code_lines(f))]
     return base + [f for f in m0 if f not in base]
 
 
