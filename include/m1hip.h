@@ -313,6 +313,22 @@ int m1_softmax_heads_fwd(const m1_head_t* heads, int nheads, float* probs, int N
 int m1_softmax_heads_bwd(const m1_head_t* heads, int nheads, const float* probs, const float* dprobs, int N,
                          int D, int H, int W, int nc, int dtype, void* stream);
 
+/* ---- Monte-Carlo inference : train_model.py:72 (--UNET_PROBA_ITER), scipy.stats.entropy ----
+ * The mean and the predictive entropy of n softmax draws without a per-draw probability tensor (csrc/mc.hip).
+ * m1_mc_accum: logits (R*B, V, nc) bf16 / fp32 = the raw head output of ONE forward pass over R replicas of the caller's B samples,
+ * replica-major (sample r*B + b is replica r of sample b).  Per (b, v) and replica: the max-subtracted fp32 softmax over nc in the
+ * operation order of m1_softmax_heads_fwd (one draw equals that kernel's output bit for bit); the R vectors are summed in replica
+ * order; accumulate == 0: sum_p (B, V, nc) fp32 = that sum (this is how the accumulator is initialised: no zero fill exists or is
+ * needed), accumulate != 0: sum_p += that sum.  samples_out (optional, (R*B, V, nc) fp32): the per-draw probabilities.
+ * nc in 2..4 (M1_ERR_UNSUPPORTED otherwise).  Pointers must be aligned to their element type; 16-byte accesses are used when every
+ * pointer is 16-byte aligned and (R == 1 or B*V*nc elements of logits are a multiple of 16 bytes), element accesses otherwise.
+ * m1_mc_finish: mean (B, V, nc) = sum_p / n_draws (IEEE division: n_draws == 1 returns the draw unchanged; mean may alias sum_p);
+ * entropy (B, V) = -sum_c mean_c * ln(mean_c) in nats, a term with mean_c == 0 contributing exactly 0.
+ * No atomics, no memset / memcpy nodes; results are bit-identical run to run. */
+int m1_mc_accum(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, int accumulate, float* samples_out,
+                void* stream);
+int m1_mc_finish(const float* sum_p, int n_draws, int B, long long V, int nc, float* mean, float* entropy, void* stream);
+
 /* ---- Focal loss on the softmax heads : losses.py:32-49 (FL: renormalise, clip [1e-7, 1-1e-7], -y log p, * y (1-p)^gamma,
  * * alpha, sum over D,H,W,C, mean over the batch; loss(): mean over the y_pred.shape[-1] / nc heads) ----
  * probs (N,V,nheads*nc) fp32 as written by m1_softmax_heads_fwd; y_true (N,V,nc) fp32 or bf16; alpha: nc HOST floats.

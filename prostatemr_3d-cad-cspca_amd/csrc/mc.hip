@@ -1,0 +1,183 @@
+// mc.hip -- Monte-Carlo inference: mean and predictive entropy of n softmax draws of the detection head (the reference's
+// --UNET_PROBA_ITER, train_model.py:72, with scipy.stats.entropy) without a per-draw probability tensor.
+//   m1_mc_accum : one forward pass over R replicas of the batch -> sum_p (+)= sum_r softmax(logits_r)        (fp32, (B,V,nc))
+//   m1_mc_finish: mean = sum_p / n, entropy = -sum_c mean_c ln(mean_c)
+// Both stream: a thread owns G consecutive voxels (G*nc elements = nc 16-byte vectors of logits) through every replica, so the
+// replica sum lives in registers and nothing is exchanged between threads (no atomics, no LDS).  The voxels behind the last whole
+// group, and everything when a pointer or the replica stride is not 16-byte aligned, take the same code with G = 1.
+// The softmax is head.hip's, operation for operation (max, expf(x - max), sum in class order, 1 / sum, product): a single draw
+// equals m1_softmax_heads_fwd bit for bit.  The file is compiled without contraction (see augment.hip for why the __f*_rn
+// intrinsics do not give that): each probability is rounded before it is added, which is what the tests' restatement counts.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+template <int NC>
+__device__ __forceinline__ void mc_softmax(float* v) {
+    float m = -3.4e38f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) m = fmaxf(m, v[c]);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { v[c] = expf(v[c] - m); s += v[c]; }
+    const float inv = 1.f / s;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = v[c] * inv;
+}
+
+// E consecutive floats: float4 accesses when the caller's group is a whole number of them (G > 1), element accesses otherwise
+template <int E, bool VEC>
+__device__ __forceinline__ void mc_ld(const float* p, float* o) {
+    if constexpr (VEC) {
+#pragma unroll
+        for (int q = 0; q < E / 4; ++q) VecIO<float, 4>::ld(p + 4 * q, o + 4 * q);
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; ++k) o[k] = p[k];
+    }
+}
+template <int E, bool VEC>
+__device__ __forceinline__ void mc_st(float* p, const float* o) {
+    if constexpr (VEC) {
+#pragma unroll
+        for (int q = 0; q < E / 4; ++q) VecIO<float, 4>::st(p + 4 * q, o + 4 * q);
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; ++k) p[k] = o[k];
+    }
+}
+
+// G voxels starting at element e0 of every replica (rstride elements apart)
+template <typename T, int NC, int G>
+__device__ __forceinline__ void mc_accum_item(const T* lg, long long rstride, int R, long long e0, float* sum_p, int accumulate,
+                                              float* samples) {
+    constexpr int E = G * NC, LV = sizeof(T) == 2 ? 8 : 4;
+    constexpr bool VEC = G > 1;
+    float old[E], acc[E];
+    if (accumulate) mc_ld<E, VEC>(sum_p + e0, old);
+    for (int r = 0; r < R; ++r) {
+        float v[E];
+        const T* p = lg + (long long)r * rstride + e0;
+        if constexpr (VEC) {
+#pragma unroll
+            for (int q = 0; q < E / LV; ++q) VecIO<T, LV>::ld(p + q * LV, v + q * LV);
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; ++k) v[k] = Act<T>::ld(p + k);
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) mc_softmax<NC>(v + g * NC);
+        if (samples) mc_st<E, VEC>(samples + (long long)r * rstride + e0, v);
+        if (r == 0) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) acc[k] = v[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; ++k) acc[k] = acc[k] + v[k];
+        }
+    }
+    if (accumulate) {
+#pragma unroll
+        for (int k = 0; k < E; ++k) acc[k] = old[k] + acc[k];
+    }
+    mc_st<E, VEC>(sum_p + e0, acc);
+}
+
+// items [0, ngroups): whole groups of G voxels; items [ngroups, ngroups + ntail): the single voxels behind them.  M = B * V.
+template <typename T, int NC>
+__global__ void __launch_bounds__(256) mc_accum_kernel(const T* __restrict__ lg, int R, long long M, long long ngroups,
+                                                       float* __restrict__ sum_p, int accumulate, float* __restrict__ samples) {
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;
+    const long long items = ngroups + (M - ngroups * G), rstride = M * NC;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        if (i < ngroups) mc_accum_item<T, NC, G>(lg, rstride, R, i * (G * NC), sum_p, accumulate, samples);
+        else mc_accum_item<T, NC, 1>(lg, rstride, R, (ngroups * G + (i - ngroups)) * NC, sum_p, accumulate, samples);
+    }
+}
+
+template <int NC, int G>
+__device__ __forceinline__ void mc_finish_item(const float* sum_p, float n, long long v0, float* mean, float* entropy) {
+    constexpr int E = G * NC;
+    constexpr bool VEC = G > 1;
+    float m[E], h[G];
+    mc_ld<E, VEC>(sum_p + v0 * NC, m);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        float a = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const float mc = m[g * NC + c] / n;
+            m[g * NC + c] = mc;
+            if (mc > 0.f) a = a - mc * logf(mc);        // (mean_c == 0: the term is exactly 0, no 0 * -inf)
+        }
+        h[g] = a;
+    }
+    mc_st<E, VEC>(mean + v0 * NC, m);
+    mc_st<G, VEC>(entropy + v0, h);
+}
+
+// (mean may alias sum_p: a thread reads its own elements before it writes them, so no __restrict__ on either)
+template <int NC>
+__global__ void __launch_bounds__(256) mc_finish_kernel(const float* sum_p, float n, long long M, long long ngroups, float* mean,
+                                                        float* __restrict__ entropy) {
+    constexpr int G = 4;
+    const long long items = ngroups + (M - ngroups * G);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        if (i < ngroups) mc_finish_item<NC, G>(sum_p, n, i * G, mean, entropy);
+        else mc_finish_item<NC, 1>(sum_p, n, ngroups * G + (i - ngroups), mean, entropy);
+    }
+}
+
+static inline bool mc_al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+template <typename T>
+static int mc_accum_launch(const void* logits, int R, long long M, int nc, float* sum_p, int accumulate, float* samples, hipStream_t st) {
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;
+    const bool vec = mc_al(logits, 16) && mc_al(sum_p, 16) && (!samples || mc_al(samples, 16)) &&
+                     (R == 1 || (M * nc * (long long)sizeof(T)) % 16 == 0);
+    const long long ngroups = vec ? M / G : 0, items = ngroups + (M - ngroups * G);
+    const dim3 grid(m1_grid_for(items, 1)), block(256);
+    const int acc = accumulate != 0;
+    switch (nc) {
+        case 2: hipLaunchKernelGGL((mc_accum_kernel<T, 2>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, acc, samples); break;
+        case 3: hipLaunchKernelGGL((mc_accum_kernel<T, 3>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, acc, samples); break;
+        default: hipLaunchKernelGGL((mc_accum_kernel<T, 4>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, acc, samples); break;
+    }
+    return m1_check_launch();
+}
+
+extern "C" int m1_mc_accum(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, int accumulate,
+                           float* samples_out, void* stream) {
+    if (m1_debug_skip("mc_accum")) return M1_OK;
+    if (!logits || !sum_p || R <= 0 || B <= 0 || V <= 0 || (dtype != M1_F32 && dtype != M1_BF16)) return M1_ERR_BAD_ARG;
+    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
+    if (!mc_al(logits, dtype == M1_BF16 ? 2 : 4) || !mc_al(sum_p, 4) || !mc_al(samples_out, 4)) return M1_ERR_BAD_ARG;
+    const long long M = (long long)B * V;
+    if (M > (1ll << 40) / R) return M1_ERR_BAD_ARG;                   // (element offsets stay far inside 63 bits)
+    const double el = (double)M * nc;
+    M1ProfScope ps("mc_accum", 0.0, el * R * (dtype == M1_BF16 ? 2 : 4) + el * 4 * (accumulate ? 2 : 1) + (samples_out ? el * R * 4 : 0.0),
+                   (hipStream_t)stream);
+    return dtype == M1_BF16 ? mc_accum_launch<bf16_t>(logits, R, M, nc, sum_p, accumulate, samples_out, (hipStream_t)stream)
+                            : mc_accum_launch<float>(logits, R, M, nc, sum_p, accumulate, samples_out, (hipStream_t)stream);
+}
+
+extern "C" int m1_mc_finish(const float* sum_p, int n_draws, int B, long long V, int nc, float* mean, float* entropy, void* stream) {
+    if (m1_debug_skip("mc_finish")) return M1_OK;
+    if (!sum_p || !mean || !entropy || n_draws <= 0 || B <= 0 || V <= 0) return M1_ERR_BAD_ARG;
+    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
+    if (!mc_al(sum_p, 4) || !mc_al(mean, 4) || !mc_al(entropy, 4)) return M1_ERR_BAD_ARG;
+    const long long M = (long long)B * V;
+    if (M > (1ll << 40)) return M1_ERR_BAD_ARG;
+    const bool vec = mc_al(sum_p, 16) && mc_al(mean, 16) && mc_al(entropy, 16);
+    const long long ngroups = vec ? M / 4 : 0, items = ngroups + (M - ngroups * 4);
+    const dim3 grid(m1_grid_for(items, 1)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    M1ProfScope ps("mc_finish", 0.0, (double)M * (2.0 * nc + 1.0) * 4, st);
+    const float n = (float)n_draws;
+    switch (nc) {
+        case 2: hipLaunchKernelGGL(mc_finish_kernel<2>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
+        case 3: hipLaunchKernelGGL(mc_finish_kernel<3>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
+        default: hipLaunchKernelGGL(mc_finish_kernel<4>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
+    }
+    return m1_check_launch();
+}

@@ -842,6 +842,59 @@ def softmax_heads(logits: Sequence[torch.Tensor], ups: Sequence[Tuple[int, int, 
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Monte-Carlo inference: n-draw mean and entropy of the detection head (mc.hip; M1.get_detect_model().predict_mc)
+# ---------------------------------------------------------------------------------------------------------
+def _no_grad_only(what: str) -> None:
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{what} is an inference op without a backward: call it under torch.no_grad()")
+
+
+def mc_accum(logits: torch.Tensor, R: int, sum_p: Optional[torch.Tensor] = None, samples: bool = False):
+    """One pass of an n-draw inference (m1_mc_accum): ``logits`` (R*B, D, H, W, nc) is the head's raw output over ``R`` replicas of
+    the caller's B samples, replica-major.  ``sum_p=None`` starts an accumulator (B, D, H, W, nc) fp32 = sum_r softmax(logits_r) --
+    written, not added to, so it needs no zero fill; a given ``sum_p`` is added to in place.  Returns ``sum_p``, or
+    ``(sum_p, per-draw probabilities (R, B, D, H, W, nc) fp32)`` with ``samples=True`` or with ``samples`` = the fp32 tensor of that
+    shape to write them into."""
+    _no_grad_only("mc_accum")
+    _req(logits, sum_p)
+    R = int(R)
+    if logits.dim() < 3 or R < 1 or int(logits.shape[0]) % R:
+        raise RuntimeError(f"mc_accum: logits {tuple(logits.shape)} do not hold {R} replicas of a batch")
+    B, nc = int(logits.shape[0]) // R, int(logits.shape[-1])
+    shape = (B, *logits.shape[1:])
+    V = logits.numel() // (R * B * nc)
+    if sum_p is None:
+        acc, sum_p = 0, torch.empty(shape, dtype=torch.float32, device=logits.device)
+    elif sum_p.dtype != torch.float32 or tuple(sum_p.shape) != shape:
+        raise RuntimeError(f"mc_accum: sum_p must be fp32 {shape}, got {sum_p.dtype} {tuple(sum_p.shape)}")
+    else:
+        acc = 1
+    draws = None
+    if isinstance(samples, torch.Tensor):                  # (the caller's own slice of an (n_draws, B, ...) tensor)
+        draws = samples
+        _req(draws)
+        if draws.dtype != torch.float32 or tuple(draws.shape) != (R, *shape):
+            raise RuntimeError(f"mc_accum: samples must be fp32 {(R, *shape)}, got {draws.dtype} {tuple(draws.shape)}")
+    elif samples:
+        draws = torch.empty((R, *shape), dtype=torch.float32, device=logits.device)
+    L.check(L.load().m1_mc_accum(_p(logits), R, B, V, nc, _dt(logits), _p(sum_p), acc, _p(draws), _stream()), "m1_mc_accum")
+    return sum_p if draws is None else (sum_p, draws)
+
+
+def mc_finish(sum_p: torch.Tensor, n: int):
+    """(mean, entropy) of ``n`` accumulated draws (m1_mc_finish): mean = sum_p / n, written over ``sum_p``; entropy (B, D, H, W) fp32 =
+    -sum_c mean_c ln(mean_c) in nats (scipy.stats.entropy's default), 0 ln 0 = 0."""
+    _no_grad_only("mc_finish")
+    _req(sum_p)
+    if sum_p.dtype != torch.float32 or sum_p.dim() < 2 or int(n) < 1:
+        raise RuntimeError("mc_finish: sum_p must be the fp32 accumulator of mc_accum and n >= 1")
+    B, nc = int(sum_p.shape[0]), int(sum_p.shape[-1])
+    ent = torch.empty(sum_p.shape[:-1], dtype=torch.float32, device=sum_p.device)
+    L.check(L.load().m1_mc_finish(_p(sum_p), int(n), B, sum_p.numel() // (B * nc), nc, _p(sum_p), _p(ent), _stream()), "m1_mc_finish")
+    return sum_p, ent
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Focal loss on the softmax heads (losses.py:32-49)
 # ---------------------------------------------------------------------------------------------------------
 class _Focal(torch.autograd.Function):

@@ -21,6 +21,9 @@ What differs from the reference, and why (its harness bugs a
     (T:121) is outside the hot path: rejected loudly.  ``--LOSS_MODE region_boundary`` (T:125) trains with
     ``losses.SoftDicePlusBoundarySurface`` (GPU distance transform, no CPU step); under data parallelism each rank takes the
     loss of its own shard and the gradient all-reduce averages it, as MirroredStrategy does per replica.
+  * ``--UNET_PROBA_ITER`` ("Iterations of Probabilistic Inference During Validation", T:72) is parsed and NOT used: this trainer
+    does not validate.  What the flag stands for is ``n_draws`` of ``model.get_detect_model().predict_mc(x, n_draws)`` (mean and
+    entropy of n draws with fresh dropout masks and latent samples, unets/networks.py), for a caller's own validation loop.
   * checkpoints are ``model_weights_NNN.npz`` (callbacks.py); the fold-finished test uses the intended file name
     (the reference formats a set literal into it, T:103).
 """

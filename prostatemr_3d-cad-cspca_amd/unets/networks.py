@@ -933,6 +933,54 @@ class M1(LoadableModel):
 
             def predict(self, x, **kw):
                 return self.forward(x, **kw)
+
+            def predict_mc(self, x, n_draws, draws_per_pass=1, return_samples=False, eps_p=None):
+                """Monte-Carlo inference (the reference's --UNET_PROBA_ITER, train_model.py:72): ``n_draws`` hypotheses of ``predict`` --
+                fresh dropout masks and, for the probabilistic model, fresh z ~ P at every level -- folded into
+                {"mean": (B,D,H,W,nc) fp32, "entropy": (B,D,H,W) fp32 in nats (scipy.stats.entropy of the mean)
+                 [, "samples": (n_draws,B,D,H,W,nc) fp32 with ``return_samples``]}; a cascaded model returns [stage 1, stage 2] of these.
+                A pass runs ``draws_per_pass`` replicas of the input stacked along the batch axis, replica-major (sample r*B + b is
+                replica r of sample b): the in-kernel draws are keyed by the element index over the whole batch, so every replica
+                draws for itself.  The head's raw logits go to ops.mc_accum, which keeps only the running sum of the probabilities;
+                ops.mc_finish divides and takes the entropy.  The {seed, step} state advances once per pass: the first draw is what
+                ``predict(x)`` returns at the current state, and the call leaves the state at step + n_draws / draws_per_pass.
+                ``eps_p`` (injected draws, as in ``forward``) only with n_draws == 1: every draw would be the same."""
+                n, R = int(n_draws), int(draws_per_pass)
+                if n < 1 or R < 1 or n % R:
+                    raise ValueError(f"predict_mc: n_draws >= 1 and draws_per_pass dividing it expected, got {n_draws} / {draws_per_pass}")
+                if eps_p is not None and n > 1:
+                    raise ValueError("predict_mc: injected eps_p with n_draws > 1 would repeat one draw n_draws times")
+                prob = outer.references.probabilistic
+                casc = outer.references.cascaded != False  # noqa: E712
+                rep = (lambda t: t.repeat(R, 1, 1, 1, 1)) if R > 1 else (lambda t: t)
+                with torch.no_grad():
+                    if casc:
+                        x1, x2 = outer._cascade_inputs(x)
+                        xin = (rep(outer._prep(x1, channels=outer.input_channels)), rep(outer._prep(x2, channels=outer.input_channels)))
+                    else:
+                        xin = rep(outer._prep(x))
+                    sums = draws = None
+                    for k in range(n // R):
+                        if casc:
+                            outer._forward_cascaded(xin, eps_p=eps_p, with_infer=prob)
+                            outs = outer._last_cascade
+                        else:
+                            outs = (outer.m1_model(xin, train_outputs=False, eps_p=eps_p) if prob else outer.m1_model(xin),)
+                        logits = [o['prob_infer_conv'] if prob else o['logits'] for o in outs]
+                        if k == 0:
+                            sums = [None] * len(logits)
+                            if return_samples:
+                                draws = [torch.empty((n, int(l.shape[0]) // R, *l.shape[1:]), dtype=torch.float32, device=l.device)
+                                         for l in logits]
+                        for j, l in enumerate(logits):
+                            r = ops.mc_accum(l, R, sums[j], samples=draws[j][k * R:(k + 1) * R] if return_samples else False)
+                            sums[j] = r[0] if return_samples else r
+                        outer.advance_rng()
+                    res = []
+                    for j, s in enumerate(sums):
+                        mean, ent = ops.mc_finish(s, n)
+                        res.append({"mean": mean, "entropy": ent, **({"samples": draws[j]} if return_samples else {})})
+                return res if casc else res[0]
         return _Detect()
 
     # ---- networks.py:209-223 ---------------------------------------------------------------------------------
