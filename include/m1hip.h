@@ -424,6 +424,28 @@ int m1_aug_gamma_stats(const float* gx, const m1_aug_params_t* table, int N, int
 int m1_aug_intensity(const float* gx, const m1_aug_params_t* table, const uint64_t* rng, uint64_t stream_id, float* out, int N,
                      int D, int H, int W, int C, int nimg, int stages, int dtype, void* ws, void* stream);
 
+/* ---- label preparation of the data generator : data_generators.py:51-72,92-97 (labels.hip) ----
+ * contour_smoothening as an integer rule (DESIGN.md "label feed"; restated from OpenCV's 8-bit bit-exact Gaussian, not pinned against
+ * cv2): per H x W slice S(y,x) = sum_dy sum_dx taps[dy+3] * taps[dx+3] * m(r(y+dy,H), r(x+dx,W)), r = reflect-101 repeated until the
+ * index is in range (0 when the extent is 1), out = (S + 32768) >> 16.  taps: 7 HOST integers >= 0 that sum to 256
+ * (data_generators.gaussian_taps_u8(7, 4.0) = 31 36 40 42 40 36 31), else M1_ERR_BAD_ARG.
+ * m1_contour_smooth_u8: in / out / scratch hold planes * H * W bytes; `iterations` repeats the pass (scratch is needed, and may be
+ * NULL otherwise, for iterations > 1); the three buffers are distinct. */
+int m1_contour_smooth_u8(const uint8_t* in, uint8_t* out, uint8_t* scratch, long long planes, int H, int W, const int* taps,
+                         int iterations, void* stream);
+enum m1_label_objective { M1_LABEL_LESION = 0, M1_LABEL_ZONAL = 1 };
+enum m1_feed_mode { M1_FEED_TRAIN = 0, M1_FEED_VALID = 1, M1_FEED_TEST = 2 };
+/* The generator's sample from the raw arrays, one launch, no memset / memcpy nodes.  ann (B,D,H,W) uint8: the raw annotation (grades
+ * for M1_LABEL_LESION: >= 2 -> 1; zones for M1_LABEL_ZONAL: == 1 -> TZ, == 2 -> PZ, each binarised on its own), ignored and
+ * allowed to be NULL for M1_FEED_TEST (all background).  Every class mask is smoothed (one iteration), then
+ *   detection (B,D,H,W,nc) fp32 = {1 - sum of the foreground masks in 8-bit arithmetic (mod 256), masks...}, nc = 2 / 3;
+ *   kl        (B,D,H,W,nc) fp32 = 0, required when probabilistic != 0 and NULL otherwise;
+ *   x_out     (B,D,H,W,keep [+ nc - 1]) fp32 = the first `keep` channels of image (B,D,H,W,C) -- keep = C for lesion (at most 4),
+ *             1 for zonal -- followed, when probabilistic, by detection[..., 1:] for M1_FEED_TRAIN and zeros otherwise.
+ * An objective or mode outside the enums, or more kept channels than 4: M1_ERR_UNSUPPORTED. */
+int m1_label_prepare(const uint8_t* ann, const float* image, float* x_out, float* detection, float* kl, int B, int D, int H, int W,
+                     int C, int objective, int mode, int probabilistic, const int* taps, void* stream);
+
 /* ---- MonteCarloDropout / Dropout : B:142-143 ; N:462-463 (Philox4x32-10, mask regenerated in bwd) ---- */
 int m1_dropout(const void* x, void* y, long long n, float rate, const uint64_t* rng, uint64_t layer_id, int dtype,
                void* stream);

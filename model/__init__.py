@@ -1,5 +1,5 @@
 """Reference-shaped import path: ``import model.unets as unets; import model.losses as losses`` (as in the
-reference's train_model.py:19-22, ``model.augmentations`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
+reference's train_model.py:19-22, ``model.augmentations`` and ``model.data_generators`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
 import importlib
 import os
 import sys
@@ -13,9 +13,11 @@ losses = _pkg.losses
 initializers = _pkg.initializers
 optim = _pkg.optim
 augmentations = _pkg.augmentations
+data_generators = _pkg.data_generators
 sys.modules[__name__ + ".unets"] = unets
 sys.modules[__name__ + ".unets.networks"] = unets.networks
 sys.modules[__name__ + ".unets.network_blocks"] = unets.network_blocks
 sys.modules[__name__ + ".unets.modelio"] = unets.modelio
 sys.modules[__name__ + ".losses"] = losses
 sys.modules[__name__ + ".augmentations"] = augmentations
+sys.modules[__name__ + ".data_generators"] = data_generators

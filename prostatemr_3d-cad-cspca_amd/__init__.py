@@ -16,5 +16,6 @@ from . import optim          # noqa: F401
 from . import unets          # noqa: F401
 from . import ddp            # noqa: F401
 from . import augmentations  # noqa: F401
+from . import data_generators  # noqa: F401
 
-__all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp", "augmentations"]
+__all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp", "augmentations", "data_generators"]

@@ -65,6 +65,11 @@ M1_AUG_MASTER, M1_AUG_ZOOM, M1_AUG_FLIP, M1_AUG_ROTATE, M1_AUG_TRANSLATE = 1, 2,
 M1_AUG_CSHIFT, M1_AUG_GAMMA, M1_AUG_POOR, M1_AUG_NOISE = 32, 64, 128, 256
 
 
+# enum m1_label_objective / m1_feed_mode
+M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
+M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
+
+
 class m1_prof_rec_t(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double), ("launches", C.c_longlong)]
@@ -141,6 +146,8 @@ SIGNATURES = {
     "m1_aug_geom": (_i, [_vp] * 5 + [_i] * 9 + [_vp, _vp]),
     "m1_aug_gamma_stats": (_i, [_vp, _vp] + [_i] * 8 + [_vp, _vp]),
     "m1_aug_intensity": (_i, [_vp, _vp, _vp, _u64, _vp] + [_i] * 8 + [_vp, _vp]),
+    "m1_contour_smooth_u8": (_i, [_vp, _vp, _vp, _ll, _i, _i, C.POINTER(_i), _i, _vp]),
+    "m1_label_prepare": (_i, [_vp] * 5 + [_i] * 8 + [C.POINTER(_i), _vp]),
     "m1_dropout": (_i, [_vp, _vp, _ll, _f, _vp, _u64, _i, _vp]),
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),

@@ -1055,6 +1055,59 @@ def aug_apply(x: torch.Tensor, y: Optional[torch.Tensor], table: torch.Tensor, s
 
 
 # ---------------------------------------------------------------------------------------------------------
+# label preparation of the data generator (labels.hip; data_generators.py is the public surface)
+# ---------------------------------------------------------------------------------------------------------
+LABEL_TILE = 32                     # tile edge of the label kernels (labels.hip LT): the sizes around it are what the tests probe
+LABEL_TAPS = (31, 36, 40, 42, 40, 36, 31)          # data_generators.gaussian_taps_u8(7, 4.0), the default of both wrappers
+_OBJECTIVES = {"lesion": L.M1_LABEL_LESION, "zonal": L.M1_LABEL_ZONAL}
+_FEED_MODES = {"train": L.M1_FEED_TRAIN, "valid": L.M1_FEED_VALID, "test": L.M1_FEED_TEST}
+
+
+def _taps(taps) -> "C.Array":
+    taps = LABEL_TAPS if taps is None else tuple(int(v) for v in taps)
+    if len(taps) != 7:
+        raise NotImplementedError(f"label kernels: only 7 taps (the reference's (7,7) kernel) are built, got {len(taps)}")
+    return (C.c_int * 7)(*taps)
+
+
+def contour_smooth(mask: torch.Tensor, iterations: int = 1, taps=None) -> torch.Tensor:
+    """contour_smoothening (data_generators.py:92-97) of a uint8 mask (..., H, W), every H x W slice on its own, as the integer rule
+    of m1_contour_smooth_u8; returns a new tensor."""
+    _req(mask)
+    if mask.dtype != torch.uint8 or mask.dim() < 2:
+        raise RuntimeError(f"contour_smooth: a uint8 mask (..., H, W) expected, got {mask.dtype} {tuple(mask.shape)}")
+    H, W = int(mask.shape[-2]), int(mask.shape[-1])
+    out = torch.empty_like(mask)
+    scratch = torch.empty_like(mask) if int(iterations) > 1 else None
+    L.check(L.load().m1_contour_smooth_u8(_p(mask), _p(out), _p(scratch), mask.numel() // max(H * W, 1), H, W, _taps(taps),
+                                          int(iterations), _stream()), "m1_contour_smooth_u8")
+    return out
+
+
+def prepare_labels(ann: Optional[torch.Tensor], image: torch.Tensor, train_obj: str = "lesion", mode: str = "train",
+                   probabilistic: bool = False, taps=None):
+    """The generator's batch from the raw arrays in one launch (m1_label_prepare): ``ann`` (B,D,H,W) uint8 grades / zones (None for
+    ``mode='test'``), ``image`` (B,D,H,W,C) fp32 -> (network input, detection, KL or None), all fp32 on the device."""
+    _req(ann, image)
+    if train_obj not in _OBJECTIVES or mode not in _FEED_MODES:
+        raise RuntimeError(f"prepare_labels: train_obj 'lesion' / 'zonal' and mode 'train' / 'valid' / 'test', got {train_obj!r}, {mode!r}")
+    if image.dim() != 5 or image.dtype != torch.float32:
+        raise RuntimeError(f"prepare_labels: an fp32 image (B,D,H,W,C) expected, got {image.dtype} {tuple(image.shape)}")
+    if ann is not None and (ann.dtype != torch.uint8 or tuple(ann.shape) != tuple(image.shape[:4])):
+        raise RuntimeError(f"prepare_labels: a uint8 annotation {tuple(image.shape[:4])} expected, got {ann.dtype} {tuple(ann.shape)}")
+    B, D, H, W, Cn = (int(v) for v in image.shape)
+    nc = 2 if train_obj == "lesion" else 3
+    keep = Cn if train_obj == "lesion" else 1
+    prob = bool(probabilistic)
+    x = torch.empty((B, D, H, W, keep + (nc - 1 if prob else 0)), dtype=torch.float32, device=image.device)
+    det = torch.empty((B, D, H, W, nc), dtype=torch.float32, device=image.device)
+    kl = torch.empty_like(det) if prob else None
+    L.check(L.load().m1_label_prepare(_p(ann), _p(image), _p(x), _p(det), _p(kl), B, D, H, W, Cn, _OBJECTIVES[train_obj],
+                                      _FEED_MODES[mode], int(prob), _taps(taps), _stream()), "m1_label_prepare")
+    return x, det, kl
+
+
+# ---------------------------------------------------------------------------------------------------------
 # dropout (standalone), cast
 # ---------------------------------------------------------------------------------------------------------
 class _Dropout(torch.autograd.Function):

@@ -9,7 +9,10 @@ What differs from the reference, and why (its harness bugs a
   * data: the reference reads ``.npy`` paths from ``.xlsx`` sheets (data_generators.py:30-90; needs pandas+openpyxl+cv2 and
     data that is not shipped).  Here ``--TRAIN_NPY_DIR`` takes a directory of ``image_*.npy`` / ``label_*.npy`` pairs, and
     without it ``--SYNTHETIC_SAMPLES`` whitened-noise volumes with a ball lesion are generated (same I/O contract:
-    ``({"image": x}, {"detection": y[, "KL": 0]})``, data_generators.py:79-88).
+    ``({"image": x}, {"detection": y[, "KL": 0]})``, data_generators.py:79-88).  ``--DATA_FEED sheet`` (a flag of this build, default
+    ``cases``) reads the reference's sheets instead: fold f takes ``TRAIN_XLSX_PREFIX + str(f+1) + '.xlsx'`` (or the ``.csv`` with the
+    same columns beside it) through ``data_generators.device_batches`` -- the reference's binarisation by grade, contour smoothing
+    and one-hot (data_generators.py:51-72,92-97), computed on the GPU from the raw image and a uint8 annotation.
   * augmentation: the reference maps ``augment_tensors`` over every sample on the CPU (T:180).  Here ``--AUGMENT 1`` (a flag of
     this build, default 0) sends every batch through ``augmentations.augment_tensors`` on the GPU with ``--AUGM_PARAMS`` and
     ``--TRAIN_OBJ`` before ``fit`` sees it, every sample with its own draws from a {seed, step} pair of the trainer's own (seeded
@@ -39,7 +42,7 @@ import numpy as np
 import torch
 
 from . import callbacks as cbs
-from . import augmentations, ddp, initializers, losses, optim, unets
+from . import augmentations, data_generators, ddp, initializers, losses, optim, unets
 from .hip import ops
 
 
@@ -119,6 +122,8 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--AUGM_PARAMS', type=float, default=[1.00, 0.25, 0.15, 10.0, True, 1.20, 0.10, 0.025, True, [0.50, 1.50]], nargs='+', action=_AugmParams)
     prsr.add_argument('--AUGMENT', type=int, default=0, help="1: train-time augmentations on the GPU (augmentations.augment_tensors with --AUGM_PARAMS)")
     # This build's data source (the reference's .xlsx sheets point at data that is not shipped)
+    prsr.add_argument('--DATA_FEED', type=str, default="cases", choices=["cases", "sheet"],
+                      help="'cases': --TRAIN_NPY_DIR / synthetic volumes; 'sheet': TRAIN_XLSX_PREFIX<fold>.xlsx (or .csv) through data_generators.device_batches")
     prsr.add_argument('--TRAIN_NPY_DIR', type=str, default=None, help="directory of image_*.npy (D,H,W,C) / label_*.npy (D,H,W) pairs")
     prsr.add_argument('--SYNTHETIC_SAMPLES', type=int, default=8, help="training samples per fold when no .npy directory is given")
     prsr.add_argument('--IMAGE_SPATIAL_DIMS', type=int, default=[20, 160, 160], nargs=3, help="(D,H,W) of synthetic volumes")
@@ -219,13 +224,20 @@ def train_fold(args, f: int, device, rank: int = 0, world: int = 1):
     IMAGE_NUM_CHANNELS = 3 if args.TRAIN_OBJ == 'lesion' else 1                 # T:151
     prob = bool(args.UNET_PROBABILISTIC)
     rng = np.random.default_rng(args.SEED + 1000 * f)
-    if args.TRAIN_NPY_DIR:
-        cases = load_npy_cases(args.TRAIN_NPY_DIR, NUM_CLASSES)
+    cases, sheet = None, None
+    if args.DATA_FEED == 'sheet':                                               # T:143-150: the fold's sheet, dims from its first image
+        sheet = data_generators.fold_sheet(args.TRAIN_XLSX_PREFIX, f)
+        paths = data_generators.read_sheet(sheet)["image_path"]
+        TRAIN_DATA_SAMPLES = len(paths)
+        IMAGE_SPATIAL_DIMS = tuple(int(v) for v in np.load(paths[0], mmap_mode="r").shape[:3])
     else:
-        cases = [synthetic_case(rng, tuple(args.IMAGE_SPATIAL_DIMS), IMAGE_NUM_CHANNELS, NUM_CLASSES)
-                 for _ in range(args.SYNTHETIC_SAMPLES)]
-    TRAIN_DATA_SAMPLES = len(cases)
-    IMAGE_SPATIAL_DIMS = tuple(int(v) for v in cases[0][0].shape[:3])           # T:150
+        if args.TRAIN_NPY_DIR:
+            cases = load_npy_cases(args.TRAIN_NPY_DIR, NUM_CLASSES)
+        else:
+            cases = [synthetic_case(rng, tuple(args.IMAGE_SPATIAL_DIMS), IMAGE_NUM_CHANNELS, NUM_CLASSES)
+                     for _ in range(args.SYNTHETIC_SAMPLES)]
+        TRAIN_DATA_SAMPLES = len(cases)
+        IMAGE_SPATIAL_DIMS = tuple(int(v) for v in cases[0][0].shape[:3])       # T:150
     steps_per_epoch = int(math.ceil(TRAIN_DATA_SAMPLES / args.BATCH_SIZE))      # T:255
 
     # Cosine annealing with warm restarts (T:112-117)
@@ -257,7 +269,11 @@ def train_fold(args, f: int, device, rank: int = 0, world: int = 1):
     assert np.mod(args.BATCH_SIZE, world) == 0, \
         'Batch size (%d) should be a multiple of the number of GPUs (%d).' % (args.BATCH_SIZE, world)          # T:170
 
-    train_gen = batches(custom_data_generator(cases, probabilistic=prob, mode='train'), args.BATCH_SIZE, device, rank, world)
+    if sheet is not None:
+        train_gen = data_generators.device_batches(sheet, train_obj=args.TRAIN_OBJ, probabilistic=prob, mode='train',
+                                                   batch_size=args.BATCH_SIZE, device=device, rank=rank, world=world)
+    else:
+        train_gen = batches(custom_data_generator(cases, probabilistic=prob, mode='train'), args.BATCH_SIZE, device, rank, world)
     if args.AUGMENT:                                                            # T:180 (off: the generator's batches, untouched)
         train_gen = augmented(train_gen, augmentations.parse_augm_params(args.AUGM_PARAMS), args.TRAIN_OBJ,
                               args.SEED + 7919 + 1000 * f, device, rank)
