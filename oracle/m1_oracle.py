@@ -242,7 +242,42 @@ class forced_activation_pattern:
         return False
 
 
+_RECORDED_PATTERN = None
+
+
+class recorded_activation_pattern:
+    """``with recorded_activation_pattern() as rec:`` -- collects the branch every tagged LeakyReLU takes on its own (the sign
+    test of its own argument): ``rec.masks[tag][k]``, k = how many times the core that owns the tag has been entered before --
+    the format ``forced_activation_pattern`` reads.  The pattern of an fp64 evaluation forced on an fp32 evaluation of the same
+    graph gives the fp32 error of the gradient of ONE piecewise-linear branch, free of the fp32 run's own kink flips."""
+
+    def __init__(self):
+        self.masks: Dict[str, Dict[int, torch.Tensor]] = {}
+        self.calls: Dict[str, int] = {}
+
+    def enter_core(self, pre: str) -> None:
+        self.calls[pre] = self.calls.get(pre, -1) + 1
+
+    def record(self, tag: str, x: torch.Tensor) -> None:
+        core = tag.split(".")[0]
+        if core.startswith("stage"):
+            core = ".".join(tag.split(".")[:2])
+        self.masks.setdefault(tag, {})[self.calls.get(core, 0)] = x.detach() >= 0
+
+    def __enter__(self):
+        global _RECORDED_PATTERN
+        self.prev, _RECORDED_PATTERN = _RECORDED_PATTERN, self
+        return self
+
+    def __exit__(self, *exc):
+        global _RECORDED_PATTERN
+        _RECORDED_PATTERN = self.prev
+        return False
+
+
 def lrelu(x: torch.Tensor, tag: Optional[str] = None) -> torch.Tensor:
+    if _RECORDED_PATTERN is not None and tag is not None:
+        _RECORDED_PATTERN.record(tag, x)
     if _FORCED_PATTERN is not None and tag is not None:
         m = _FORCED_PATTERN.lookup(tag)
         if m is not None:
@@ -358,6 +393,8 @@ def m1core_forward(P: Dict[str, torch.Tensor], pre: str, cfg: M1Config, inputs: 
     dm = drop_masks or {}
     if _FORCED_PATTERN is not None:
         _FORCED_PATTERN.enter_core(pre)
+    if _RECORDED_PATTERN is not None:
+        _RECORDED_PATTERN.enter_core(pre)
     inputs = _st(inputs, "input")
     deep_sup = cfg.deep_supervision if deep_supervision is None else deep_supervision
     o = CoreOut()

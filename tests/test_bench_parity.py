@@ -19,7 +19,7 @@ import torch
 
 from oracle import m1_oracle as O
 from test_hip_model import _ball_target, _check_grads, _oracle_loss_and_grads
-from util import C1_FILTERS, C1_STRIDES, PKG, activation_pattern, build_m1, load_params_into, ops, rnd
+from util import C1_FILTERS, C1_STRIDES, PKG, FlatGradView, activation_pattern, build_m1, load_params_into, ops, rnd
 
 pytestmark = pytest.mark.gpu
 README_FILTERS = (32, 64, 128, 256, 512)
@@ -209,15 +209,7 @@ def test_flat_buffer_training_path_vs_oracle_gradients(dev):
     orc = _oracle_loss_and_grads(cfg, P, x, tgt, eps, masks=ap.masks)
     loss_o, o, g64 = orc[torch.float64]
     assert abs(float(loss) - float(loss_o)) < 1e-3 * abs(float(loss_o))
-    byid = {id(p): gv for p, gv in zip(opt.flatp.params, opt.flatp.gviews)}
-
-    class _View:          # _check_grads reads .named_parameters() / .grad
-        def named_parameters(self_):
-            for n, p in m.named_parameters():
-                q = torch.nn.Parameter(p.detach(), requires_grad=False)
-                q.grad = byid[id(p)].reshape(p.shape).clone()
-                yield n, q
-    _check_grads(_View(), g64, orc[torch.float32][2])
+    _check_grads(FlatGradView(m, opt.flatp), g64, orc[torch.float32][2])
 
 
 def test_loss_curve_bf16_tracks_fp32_over_20_steps(dev):

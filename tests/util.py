@@ -57,6 +57,21 @@ def build_m1(cfg, device, dtype=torch.float32, **extra):
     return m
 
 
+class FlatGradView:
+    """What test_hip_model._check_grads reads (``.named_parameters()`` / ``.grad``) over the optimiser's FLAT gradient buffer:
+    every parameter of ``model`` paired with its slice of ``flatp`` (optim.FlatParams, after ``gather_grads()``)."""
+
+    def __init__(self, model, flatp):
+        self.model = model
+        self.byid = {id(p): gv for p, gv in zip(flatp.params, flatp.gviews)}
+
+    def named_parameters(self):
+        for n, p in self.model.named_parameters():
+            q = torch.nn.Parameter(p.detach(), requires_grad=False)
+            q.grad = self.byid[id(p)].reshape(p.shape).clone()
+            yield n, q
+
+
 class activation_pattern:
     """``with activation_pattern(model) as ap: model(x)`` records, through forward hooks only, which branch every LeakyReLU
     of the HIP path took: ``ap.masks[tag][k]`` = boolean CPU tensor of the k-th pass through the core that owns the layer,
