@@ -15,7 +15,8 @@ dropd0 at rate/2 (networks.py:523), log-sigma clip +-0.1 (networks.py:642).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+import dataclasses
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -40,6 +41,50 @@ class Input:
 
 def _same_out(size, s):
     return -(-int(size) // int(s))
+
+
+def _cat_c(ts):
+    """Channels of the virtual concat of ``ts``."""
+    return sum(int(t.shape[-1]) for t in ts)
+
+
+@dataclasses.dataclass(frozen=True)
+class _Pruning:
+    """What one pass through an ``M1Core`` evaluates and on which part of the batch (``M1Core.forward`` ``need`` / ``tail_from``).
+    Decoder stage k is the concat ``uconv{3-k}_`` with the layers that produce it, latent level k the head / latent decoder at that
+    resolution; the encoder counts as stage -1."""
+    n_lat: int                 # leading levels that have a latent
+    full: bool                 # the caller reads more than the latent heads
+    n_pr: int                  # decoder stages / latent-decoder levels the latent heads depend on
+    n_up: int                  # latent-decoder levels evaluated (dec_hi + sersp)
+    n_stage: int               # decoder concat stages evaluated (uconv3_ ... uconv0_)
+    tail: Optional[int]        # stages / levels >= n_pr run on the batch slice [tail:], the second of two stacked passes
+
+    @classmethod
+    def of(cls, latent_dims, need, tail_from):
+        """``latent_dims``: ``prob_latent_dims`` of a probabilistic core (zeros at the tail), None for a deterministic one, which
+        always runs in full on the whole batch."""
+        prob = latent_dims is not None
+        n_lat = 0
+        while prob and n_lat < 4 and latent_dims[n_lat] != 0:
+            n_lat += 1
+        full = not (prob and need == "latents")
+        n_pr = max(0, n_lat - 1)
+        n_run = 4 if full else n_pr
+        return cls(n_lat=n_lat, full=full, n_pr=n_pr, n_up=n_run, n_stage=n_run,
+                   tail=int(tail_from) if (full and prob and tail_from) else None)
+
+    def T(self, t):
+        """``t`` for a reader on the slice."""
+        return ops.batch_tail(t, self.tail) if self.tail is not None else t
+
+    def tl(self, k):
+        """Stage / level k runs on the slice."""
+        return self.tail is not None and k >= self.n_pr
+
+    def X(self, t, a, b):
+        """``t``, made at stage a, for its reader at stage b: sliced iff b runs on the slice and a does not."""
+        return self.T(t) if (self.tl(b) and not self.tl(a)) else t
 
 
 # ============================================================================================================
@@ -172,9 +217,6 @@ class M1Core(nn.Module):
         # networks.py:534-565
         if self.probabilistic:
             assert len(self.prob_latent_dims) == 4, "prob_latent_dims needs 4 entries (networks.py:534-537)"
-            nz = [v != 0 for v in self.prob_latent_dims]
-            assert all(nz[i] or not any(nz[i:]) for i in range(4)), \
-                "prob_latent_dims must have its zeros at the tail: prob_z_q is indexed by level (networks.py:645,669,693,717)"
             fr, kr, sr, rr = F[::-1], K[::-1], S[::-1], R[::-1]
             skipc = [2 * F[3], (3 if dn else 2) * F[2], (4 if dn else 2) * F[1], (5 if dn else 2) * F[0]]
             for lvl in range(4):
@@ -244,44 +286,42 @@ class M1Core(nn.Module):
         dropout draw -- behind ``serse1`` (networks.py:579-582) -- so the stem and ``serse1``'s convolutions and norms run ONCE on B
         samples and the block's last kernel writes both halves, each behind its own draw (SEResNetBottleNeck.forward ``dup``); their
         backward runs once on the sum of the halves' gradients.  From ``conv1`` on the batch is 2B as if the input had been stacked."""
-        outputs = {}
         mark = mark if mark is not None else (lambda *_: None)
-        S = self.strides
-        fo = ops.fanout
-        prob, dense = self.probabilistic, self.dense_skip
-        n_lat = 0
-        if prob:
-            while n_lat < 4 and self.prob_latent_dims[n_lat] != 0:
-                n_lat += 1
-        full = not (prob and need == "latents")
-        n_pr = max(0, n_lat - 1)                       # decoder stages / latent-decoder levels the latent heads depend on
-        n_up = 4 if full else n_pr                     # latent-decoder levels evaluated (dec_hi + sersp)
-        n_stage = 4 if full else n_pr                  # decoder concat stages evaluated (uconv3_ ... uconv0_)
-        tail = int(tail_from) if (full and prob and tail_from) else None
-        T = (lambda t: ops.batch_tail(t, tail)) if tail is not None else (lambda t: t)   # batch slice of the second stacked pass
-        tl = lambda k: tail is not None and k >= n_pr                              # stage / level k runs on the slice
-        # X(t, from_k, to_k): tensor produced at stage from_k, consumed at stage to_k
-        X = lambda t, a, b: T(t) if (tl(b) and not tl(a)) else t
+        P = _Pruning.of(self.prob_latent_dims if self.probabilistic else None, need, tail_from)
         # SE gates are functions of parameters only: one launch for the blocks this pass will run
         used = [self.serse1, self.serse2, self.serse3, self.serse4]
-        used += [m for k, m in enumerate((self.sersd3, self.sersd2, self.sersd1)) if n_stage > k + 1]
-        if not prob:
+        used += [m for k, m in enumerate((self.sersd3, self.sersd2, self.sersd1)) if P.n_stage > k + 1]
+        if not self.probabilistic:
             used.append(self.sersd0)
         else:
-            used += [getattr(self, "sersp" + str(3 - lvl)) for lvl in range(n_up)]
+            used += [getattr(self, "sersp" + str(3 - lvl)) for lvl in range(P.n_up)]
         SEResNetBottleNeck.precompute_gates(used)
-        if z_ready is not None and _os.environ.get("M1_LANE_FWD_OVERLAP", "1") == "0":
-            # debug switch: join the posterior lane HERE, before the first conv of this pass, instead of where the first z is read (the
-            # forward passes of the two networks then do not overlap, 24.7 -> 25.7 ms per C3 step).  Round 4 shipped this for a few
-            # hours while the replayed graph of the step produced run-dependent gradients; the cause turned out to be packed fp32 VALU
-            # instructions next to MFMA kernels (csrc/Makefile NOPK, DESIGN.md 5), not the overlap.
-            z_ready(); z_ready = None
+        self._shapes = {}
+        convm, m_use, gate_src = self._encoder(inputs, P, dup_first, mark)
+        att_conv, brs = self._gates(P, gate_src, m_use, dup_first)
+        uconv0_, skips, u_h = self._decoder(P, m_use, att_conv, brs, mark)
+        if not self.probabilistic:
+            return self._output_heads(uconv0_, u_h)
+        # In the probabilistic training graph nothing downstream of sersd0/logits reaches an output
+        # (networks.py:389 takes an empty slice; SURVEY 7.3): the deterministic head is skipped there.
+        distributions, used_latents, feats = self._latent_branch(P, convm, m_use, skips, prob_mean, prob_z_q, eps, eps_first_half,
+                                                                 z_ready, mark)
+        return {'prob_distributions': distributions,      # raw (mu|logsigma) maps; sigma = exp(clip(logsigma,+-0.1))
+                'prob_used_latents': used_latents,
+                'prob_decoder_features': feats if P.full else None}
+
+    def _encoder(self, inputs, P, dup_first, mark):
+        """Stem and the four strided SE blocks (networks.py:574-582).  Returns ``convm``, its aliases ``m_use`` (one per reader, popped
+        in the order gates, ``convtd3``, coarsest latent head, coarsest latent decoder) and the gates' inputs, coarsest first.
+
+        A tensor read by several layers is handed out as one alias per reader (ops.fanout, hip/gradslot.py): the readers' backward
+        kernels then sum its gradient in one buffer instead of autograd adding per-reader gradient tensors."""
+        fo = ops.fanout
+        split = lambda t, on: fo(t, 2) if on else (t, None)
+        n_stage = P.n_stage
         # networks.py:574-576
         x_raw, s0 = self.conve0(inputs, stats=True)
         x = self.norme0(x_raw, 0.1, s0)
-        # A tensor read by several layers is handed out as one alias per reader (ops.fanout, hip/gradslot.py): the readers' backward kernels
-        # then sum its gradient in one buffer instead of autograd adding per-reader gradient tensors.
-        split = lambda t, on: fo(t, 2) if on else (t, None)
         # networks.py:579-582 (dropout fused into the block's last kernel)
         x_e, x_a = split(x, n_stage > 3)
         conv1 = self.serse1(x_e, dropout=self.drope1, dup=dup_first)
@@ -293,181 +333,139 @@ class M1Core(nn.Module):
         c3_e, c3_a = split(conv3, n_stage > 0)
         convm = self.serse4(c3_e, dropout=self.drope4)
         # readers of convm: the gates, convtd3 (+ the coarsest latent head and latent decoder)
-        n_m = n_stage + (1 if n_stage > 0 else 0) + ((1 if n_lat > 0 else 0) + (1 if n_up > 0 else 0) if prob else 0)
+        n_m = n_stage + (1 if n_stage > 0 else 0)
+        if self.probabilistic:
+            n_m += (1 if P.n_lat > 0 else 0) + (1 if P.n_up > 0 else 0)
         m_use = list(fo(convm, n_m)) if n_m > 1 else [convm]
-        # networks.py:585-588
-        # the gates depend on the encoder only: each runs on a side stream of its own, next to the decoder (ops.branch, hip/streams.py),
-        # and is joined where the decoder first reads it
-        dvc = convm.device
-        att_conv = [None] * 4
-        brs = [None] * 4
-        for k, (gate, src) in enumerate(((self.att3, c3_a), (self.att2, c2_a), (self.att1, c1_a), (self.att0, x_a))):
-            if n_stage > k:
-                with ops.branch(dvc, 1 + k) as br:
-                    if k == 3 and dup_first:
-                        # the stem output holds B samples: it IS the batch slice of the second stacked pass, else both halves
-                        xg = src if tl(k) else torch.cat([src, src], dim=0)
-                    else:
-                        xg = X(src, -1, k)
-                    att_conv[k], _ = gate(xg, X(m_use.pop(), -1, k))
-                brs[k] = br
-        att_conv3, att_conv2, att_conv1, att_conv0 = att_conv
+        self._shapes.update({"inputs": tuple(inputs.shape) if isinstance(inputs, torch.Tensor) else (*inputs[0].shape[:-1], _cat_c(inputs)),
+                             "x": tuple(x.shape), "conv1": tuple(conv1.shape), "conv2": tuple(conv2.shape), "conv3": tuple(conv3.shape),
+                             "convm": tuple(convm.shape)})
+        return convm, m_use, (c3_a, c2_a, c1_a, x_a)
+
+    def _gates(self, P, gate_src, m_use, dup_first):
+        """The attention gates of the stages that run (networks.py:585-588): ``att_conv[k]`` feeds decoder stage k.  The gates depend
+        on the encoder only: each runs on a side stream of its own, next to the decoder (ops.branch, hip/streams.py), and is joined
+        where the decoder first reads it (``brs[k].join``)."""
+        att_conv, brs = [None] * 4, [None] * 4
+        for k in range(P.n_stage):
+            src = gate_src[k]
+            with ops.branch(src.device, 1 + k) as br:
+                if k == 3 and dup_first:
+                    # the stem output holds B samples: it IS the batch slice of the second stacked pass, else both halves
+                    xg = src if P.tl(k) else torch.cat([src, src], dim=0)
+                else:
+                    xg = P.X(src, -1, k)
+                att_conv[k], _ = getattr(self, f"att{3 - k}")(xg, P.X(m_use.pop(), -1, k))
+            brs[k] = br
+            self._shapes[f"att_conv{3 - k}"] = tuple(att_conv[k].shape)
+        return att_conv, brs
+
+    def _decoder(self, P, m_use, att_conv, brs, mark):
+        """The nested decoder (networks.py:591-624): stage k builds the concat ``uconv{3-k}_`` from the transposed conv ``convtd{3-k}`` of
+        the stage before (``sersd{4-k}`` of its concat; ``convm`` at stage 0), with ``dense_skip`` the j-th upsampling of stage k-j's
+        transposed conv, and the gate ``att{3-k}``.  Returns the last concat, the members of every concat for the latent branch
+        (aliases of their own while the decoder goes on reading them) and ``u_h[i]`` = ``uconv{i}`` for the deep-supervision heads."""
+        fo = ops.fanout
+        prob, dense = self.probabilistic, self.dense_skip
         heads_on = self.deep_supervision and not prob
-        cat_c = lambda ts: sum(int(t.shape[-1]) for t in ts)
-        self._shapes = {"inputs": tuple(inputs.shape) if isinstance(inputs, torch.Tensor) else (*inputs[0].shape[:-1], cat_c(inputs)),
-                        "x": tuple(x.shape), "conv1": tuple(conv1.shape), "conv2": tuple(conv2.shape), "conv3": tuple(conv3.shape),
-                        "convm": tuple(convm.shape)}
-        for k, a in enumerate(att_conv):
-            if a is not None:
-                self._shapes[f"att_conv{3 - k}"] = tuple(a.shape)
-        uconv3_p = uconv2_p = uconv1_p = uconv0_ = None
-        u1_h = u2_h = u3_h = None
-        # networks.py:591-597   (stage k = the concat uconv{3-k}_; X(t, a, b) slices a tensor made at stage a for a reader at stage b)
-        if n_stage > 0:
-            deconv3 = self.convtd3(X(m_use.pop(), -1, 0))
-            mark("a", deconv3)
-            if dense and n_stage > 1:
-                deconv3, d3 = fo(deconv3, 2)
-                deconv3_up1 = self.convtd3_up1(X(d3, 0, 1))
-                if n_stage > 2:
-                    deconv3_up1, d3u1 = fo(deconv3_up1, 2)
-                    deconv3_up2 = self.convtd3_up2(X(d3u1, 1, 2))
-                    if n_stage > 3:
-                        deconv3_up2, d3u2 = fo(deconv3_up2, 2)
-                        deconv3_up3 = self.convtd3_up3(X(d3u2, 2, 3))
-            brs[0].join(att_conv3)
-            uconv3_ = [deconv3, att_conv3]
-            self._shapes["uconv3_"] = (*deconv3.shape[:-1], cat_c(uconv3_))
-            if prob and n_stage > 1:
-                uconv3_, uconv3_p = (list(v) for v in zip(*[fo(t, 2) for t in uconv3_]))
-            elif prob:
-                uconv3_p = uconv3_
-        if n_stage > 1:
-            uconv3 = self.sersd3([X(t, 0, 1) for t in uconv3_], dropout=self.dropd3)      # (its output feeds stage 1)
-            self._shapes["uconv3"] = tuple(uconv3.shape)
-            u3_up, u3_h = fo(uconv3, 2) if heads_on else (uconv3, uconv3)
-            # networks.py:600-607
-            deconv2 = self.convtd2(u3_up)
-            if dense and n_stage > 2:
-                deconv2, d2 = fo(deconv2, 2)
-                deconv2_up1 = self.convtd2_up1(X(d2, 1, 2))
-                if n_stage > 3:
-                    deconv2_up1, d2u1 = fo(deconv2_up1, 2)
-                    deconv2_up2 = self.convtd2_up2(X(d2u1, 2, 3))
-            brs[1].join(att_conv2)
-            uconv2_ = [deconv2, deconv3_up1, att_conv2] if dense else [deconv2, att_conv2]
-            self._shapes["uconv2_"] = (*deconv2.shape[:-1], cat_c(uconv2_))
-            if prob and n_stage > 2:
-                uconv2_, uconv2_p = (list(v) for v in zip(*[fo(t, 2) for t in uconv2_]))
-            elif prob:
-                uconv2_p = uconv2_
-        if n_stage > 2:
-            uconv2 = self.sersd2([X(t, 1, 2) for t in uconv2_], dropout=self.dropd2)
-            self._shapes["uconv2"] = tuple(uconv2.shape)
-            u2_up, u2_h = fo(uconv2, 2) if heads_on else (uconv2, uconv2)
-            # networks.py:610-616
-            deconv1 = self.convtd1(u2_up)
-            if dense and n_stage > 3:
-                deconv1, d1 = fo(deconv1, 2)
-                deconv1_up1 = self.convtd1_up1(X(d1, 2, 3))
-            brs[2].join(att_conv1)
-            uconv1_ = [deconv1, deconv2_up1, deconv3_up2, att_conv1] if dense else [deconv1, att_conv1]
-            self._shapes["uconv1_"] = (*deconv1.shape[:-1], cat_c(uconv1_))
-            if prob and n_stage > 3:
-                uconv1_, uconv1_p = (list(v) for v in zip(*[fo(t, 2) for t in uconv1_]))
-            elif prob:
-                uconv1_p = uconv1_
-        if n_stage > 3:
-            uconv1 = self.sersd1([X(t, 2, 3) for t in uconv1_], dropout=self.dropd1)
-            self._shapes["uconv1"] = tuple(uconv1.shape)
-            u1_up, u1_h = fo(uconv1, 2) if heads_on else (uconv1, uconv1)
-            # networks.py:619-624
-            deconv0 = self.convtd0(u1_up)
-            brs[3].join(att_conv0)
-            uconv0_ = [deconv0, deconv1_up1, deconv2_up2, deconv3_up3, att_conv0] if dense else [deconv0, att_conv0]
-            self._shapes["uconv0_"] = (*deconv0.shape[:-1], cat_c(uconv0_))
+        chains, skips, u_h = [], [], {}          # chains[k] = [deconv{3-k}, deconv{3-k}_up1, deconv{3-k}_up2, ...]
+        concat = None
+        for k in range(P.n_stage):
+            if k == 0:
+                d = self.convtd3(P.X(m_use.pop(), -1, 0))
+                mark("a", d)
+            else:
+                u = getattr(self, f"sersd{4 - k}")([P.X(t, k - 1, k) for t in concat], dropout=getattr(self, f"dropd{4 - k}"))
+                self._shapes[f"uconv{4 - k}"] = tuple(u.shape)
+                u, u_h[4 - k] = fo(u, 2) if heads_on else (u, u)
+                d = getattr(self, f"convtd{3 - k}")(u)
+            chain, j = [d], 1
+            while dense and P.n_stage > k + j:       # made here, at the batch of the stage k+j that reads it
+                chain[-1], a = fo(chain[-1], 2)
+                chain.append(getattr(self, f"convtd{3 - k}_up{j}")(P.X(a, k + j - 1, k + j)))
+                j += 1
+            chains.append(chain)
+            brs[k].join(att_conv[k])
+            concat = [chains[k - i][i] for i in range(k + 1 if dense else 1)] + [att_conv[k]]
+            self._shapes[f"uconv{3 - k}_"] = (*chain[0].shape[:-1], _cat_c(concat))
+            if prob and P.n_stage > k + 1:
+                concat, lat = (list(v) for v in zip(*[fo(t, 2) for t in concat]))
+            else:
+                lat = concat
+            skips.append(lat)
+        return concat, skips, u_h
 
-        # In the probabilistic training graph nothing downstream of sersd0/logits reaches an output
-        # (networks.py:389 takes an empty slice): the deterministic head is skipped there.
-        y__ = None
-        if not self.probabilistic:
-            uconv0 = self.sersd0(uconv0_, dropout=self.dropd0)                     # networks.py:624
-            y__ = self.logits(uconv0)                                              # networks.py:627
-            self._shapes["uconv0"] = tuple(uconv0.shape); self._shapes["y__"] = tuple(y__.shape)
+    def _latent_branch(self, P, convm, m_use, skips, prob_mean, prob_z_q, eps, eps_first_half, z_ready, mark):
+        """The hierarchical latent branch (networks.py:633-734): per level the head ``mu_logsig``, the latent z (given, the mean, or a
+        draw) and the latent decoder ``dec_hi`` + ``sersp`` over the decoder's concat of that level.  Returns the raw heads, the latents
+        and the features of the last level evaluated."""
+        fo = ops.fanout
+        distributions, used_latents = [], []
+        feats = convm
+        zi = 0
+        for lvl in range(4 if P.full else P.n_lat):
+            sfx = str(3 - lvl)
+            Ld = self.prob_latent_dims[lvl]
+            up_on = lvl < P.n_up
+            if lvl == 0:
+                f_ml = m_use.pop() if Ld != 0 else None
+                f_up = m_use.pop() if up_on else None
+            elif Ld != 0 and up_on:
+                f_ml, f_up = fo(feats, 2)
+            else:
+                f_ml = f_up = feats
+            if up_on:
+                f_up = P.X(f_up, lvl - 1, lvl)     # the latent decoder continues on the slice; the head below still sees the whole batch
+            if Ld != 0:
+                ml = getattr(self, "mu_logsig" + sfx)(f_ml)                    # networks.py:639 (mu | logsigma)
+                if prob_z_q is not None:                                       # networks.py:645
+                    if z_ready is not None:
+                        z_ready(); z_ready = None
+                    z = prob_z_q[lvl]
+                elif prob_mean:                                                # networks.py:646
+                    z = ops.latent_sample(ml, None, True)
+                elif eps is None and getattr(self, "rng", None) is not None:   # networks.py:647, the draw made in the kernel
+                    z = ops.latent_sample(ml, None, False, stacked=eps_first_half, rng=self.rng,
+                                          stream_id=self.latent_stream_id + lvl)
+                else:                                                          # networks.py:647 with injected (or host-made) draws
+                    nb = int(ml.shape[0]) // 2 if eps_first_half else int(ml.shape[0])
+                    e = eps[zi] if eps is not None else torch.randn((nb, *ml.shape[1:-1], Ld), device=ml.device,
+                                                                     dtype=torch.float32)
+                    if e.dtype != ml.dtype or not e.is_contiguous():
+                        e = e.to(ml.dtype).contiguous()                              # draws in the activation storage type
+                    z = ops.latent_sample(ml, e, False, stacked=eps_first_half)
+                zi += 1
+                distributions.append(ml)
+                used_latents.append(z)
+                if lvl == 0 and prob_z_q is None:
+                    mark("a", ml)           # reached through z (otherwise only through a KL term: the caller marks it)
+                if not up_on:
+                    break                   # the finest latent head of a latents-only pass: nothing further is consumed
+                z_up = P.X(z, lvl - 1, lvl)             # (z comes from the head: the whole batch)
+                if z_up is not z:
+                    z_up = z_up.contiguous()
+                up = getattr(self, "dec_hi" + sfx)([z_up, f_up])               # networks.py:652-653
+            else:
+                up = getattr(self, "dec_hi" + sfx)(f_up)                       # networks.py:655-656
+            if lvl == 0:
+                mark("a", up)
+            feats = getattr(self, "sersp" + sfx)([up, *skips[lvl]], dropout=getattr(self, "dropp" + sfx))
+        return distributions, used_latents, feats
 
-        ds_ops = []
-        if self.probabilistic:                                                     # networks.py:633-734
-            distributions, used_latents = [], []
-            skips = [uconv3_p, uconv2_p, uconv1_p, uconv0_]
-            feats = convm
-            zi = 0
-            for lvl in range(4 if full else n_lat):
-                sfx = str(3 - lvl)
-                Ld = self.prob_latent_dims[lvl]
-                up_on = lvl < n_up
-                if lvl == 0:
-                    f_ml = m_use.pop() if Ld != 0 else None
-                    f_up = m_use.pop() if up_on else None
-                elif Ld != 0 and up_on:
-                    f_ml, f_up = fo(feats, 2)
-                else:
-                    f_ml = f_up = feats
-                if up_on and tl(lvl) and not tl(lvl - 1):
-                    f_up = T(f_up)                     # the latent decoder continues on the slice; the head below still sees the whole batch
-                if Ld != 0:
-                    ml = getattr(self, "mu_logsig" + sfx)(f_ml)                    # networks.py:639 (mu | logsigma)
-                    if prob_z_q is not None:                                       # networks.py:645
-                        if z_ready is not None:
-                            z_ready(); z_ready = None
-                        z = prob_z_q[lvl]
-                    elif prob_mean:                                                # networks.py:646
-                        z = ops.latent_sample(ml, None, True)
-                    elif eps is None and getattr(self, "rng", None) is not None:   # networks.py:647, the draw made in the kernel
-                        z = ops.latent_sample(ml, None, False, stacked=eps_first_half, rng=self.rng,
-                                              stream_id=self.latent_stream_id + lvl)
-                    else:                                                          # networks.py:647 with injected (or host-made) draws
-                        nb = int(ml.shape[0]) // 2 if eps_first_half else int(ml.shape[0])
-                        e = eps[zi] if eps is not None else torch.randn((nb, *ml.shape[1:-1], Ld), device=ml.device,
-                                                                         dtype=torch.float32)
-                        if e.dtype != ml.dtype or not e.is_contiguous():
-                            e = e.to(ml.dtype).contiguous()                              # draws in the activation storage type
-                        z = ops.latent_sample(ml, e, False, stacked=eps_first_half)
-                    zi += 1
-                    distributions.append(ml)
-                    used_latents.append(z)
-                    if lvl == 0 and prob_z_q is None:
-                        mark("a", ml)           # reached through z (otherwise only through a KL term: the caller marks it)
-                    if not up_on:
-                        break                   # the finest latent head of a latents-only pass: nothing further is consumed
-                    if tl(lvl) and z.shape[0] != f_up.shape[0]:
-                        z = T(z).contiguous()
-                    up = getattr(self, "dec_hi" + sfx)([z, f_up])                  # networks.py:652-653
-                else:
-                    up = getattr(self, "dec_hi" + sfx)(f_up)                       # networks.py:655-656
-                if lvl == 0:
-                    mark("a", up)
-                feats = getattr(self, "sersp" + sfx)([up, *[X(t, lvl, lvl) if t.shape[0] == up.shape[0] else T(t) for t in skips[lvl]]],
-                                                     dropout=getattr(self, "dropp" + sfx))
-                if lvl < 3:
-                    ds_ops.append(feats)                                           # networks.py:657,681,705
-            outputs['prob_distributions'] = distributions      # raw (mu|logsigma) maps; sigma = exp(clip(logsigma,+-0.1))
-            outputs['prob_used_latents'] = used_latents
-            outputs['prob_decoder_features'] = feats if full else None
-
-        # networks.py:737-757
-        if y__ is not None:
-            heads, ups = [y__], [(1, 1, 1)]
-            if self.deep_supervision:
-                s1 = S[1]
-                s12 = tuple(a * b for a, b in zip(S[1], S[2]))
-                s123 = tuple(a * b * c for a, b, c in zip(S[1], S[2], S[3]))
-                heads += [self.dsy1_logits(u1_h), self.dsy2_logits(u2_h), self.dsy3_logits(u3_h)]
-                ups += [s1, s12, s123]
-            outputs['y_softmax'] = ops.softmax_heads(heads, ups)
-            outputs['logits'] = y__
-            outputs['_heads'] = heads
-            outputs['_ups'] = ups
-        return outputs
+    def _output_heads(self, uconv0_, u_h):
+        """``sersd0``, the logits and the deep-supervision heads of the deterministic core (networks.py:624-627, 737-757)."""
+        uconv0 = self.sersd0(uconv0_, dropout=self.dropd0)                     # networks.py:624
+        y__ = self.logits(uconv0)                                              # networks.py:627
+        self._shapes["uconv0"] = tuple(uconv0.shape); self._shapes["y__"] = tuple(y__.shape)
+        heads, ups = [y__], [(1, 1, 1)]
+        if self.deep_supervision:
+            S = self.strides
+            s1 = S[1]
+            s12 = tuple(a * b for a, b in zip(S[1], S[2]))
+            s123 = tuple(a * b * c for a, b, c in zip(S[1], S[2], S[3]))
+            heads += [self.dsy1_logits(u_h[1]), self.dsy2_logits(u_h[2]), self.dsy3_logits(u_h[3])]
+            ups += [s1, s12, s123]
+        return {'y_softmax': ops.softmax_heads(heads, ups), 'logits': y__, '_heads': heads, '_ups': ups}
 
     def summary(self):
         """Stage-shape printout of networks.py:761-782 (uses the shapes of the last forward)."""
@@ -562,131 +560,124 @@ class M1Net(nn.Module):
         return lambda group, t: gm(prefix + group, t)
 
     def forward(self, inputs: torch.Tensor, eps_q=None, eps_p=None, with_infer=False, train_outputs=True):
-        outputs: Dict[str, torch.Tensor] = {}
-        nc = self.num_classes
+        summarise = self.show_summary and not self._summarised
         if not self.probabilistic:
-            o = self.core(inputs, prob_mean=False, prob_z_q=None, mark=self._marker("core."))   # networks.py:281 (+ App. C-1)
-            outputs['y_softmax'] = o['y_softmax']
-            outputs['logits'] = o['logits']
-            outputs['_heads'], outputs['_ups'] = o['_heads'], o['_ups']
-            if self.show_summary and not self._summarised:
-                print('--------------------------------------------------------------------')
-                print('Deterministic 3D U-Net (Type: M1)')
-                print('--------------------------------------------------------------------')
-                self.core.summary()
-                print('--------------------------------------------------------------------')
-                self._summarised = True
+            outputs = self._deterministic_pass(inputs)
         else:
-            C = int(inputs.shape[-1])
+            outputs = {}
+            nc, C = self.num_classes, int(inputs.shape[-1])
             # networks.py:300-301 -- channel slices as contiguous tensors (off-by-one reproduced, App. C-2)
             image = inputs[..., :C - (nc - 1)].contiguous()
             label = inputs[..., C - (nc - 1) - 1:C - 1].contiguous()
             # tf.concat([image, label]): materialised when it is the few-channel network input (one 16-byte segment per voxel
             # lets the stem's weight gradient take the padded tap-fused path: 0.85 -> 0.15 ms per step), virtual otherwise
             post_in = torch.cat([image, label], dim=-1).contiguous() if C <= 8 else [image, label]
-            if train_outputs and self.stack_passes and not (self.show_summary and not self._summarised):
-                # The four training passes (networks.py:348,349,351,352) as TWO, stacked along the batch axis: every op of the
-                # model is per sample (InstanceNorm statistics, SE gate, dropout draw per element), so
-                #   posterior([x; x], eps = [eps; 0])        = [q_sample; q_mean]       (z = mu + sigma*0 = mu: the prob_mean pass)
-                #   prior([img; img], z = [z_sample; z_mean]) = [p_z_q; p_z_qm]
-                # with half the launches at twice the batch (a 2-volume batch leaves the deep levels with 1,000-8,000 voxels per
-                # launch).  Only p_z_qm needs the decoder features: the layers behind the latent heads run on the batch slice
-                # [B:] (M1Core.forward tail_from); the posterior passes and p_z_q are latents-only (need="latents").
-                B = int(image.shape[0])
-                mq, mp = self._marker("posterior."), self._marker("prior.")
-                dup = lambda t: torch.cat([t, t], dim=0)
-                # both halves of a stacked pass read the SAME input: everything in front of the first dropout draw (stem + serse1 up to
-                # its last kernel) is one computation, run once on B samples (M1Core.forward dup_first; M1_DEDUP_PREFIX=0: stack the input)
-                vec = 8 if image.dtype == torch.bfloat16 else 4
-                share = (_os.environ.get("M1_DEDUP_PREFIX", "1") != "0" and all(
-                    (not c.serse1.identity_residual) and c.serse1.filters % vec == 0 for c in (self.prior, self.posterior)))
-                if share:
-                    post2 = post_in
-                else:
-                    post2 = dup(post_in) if isinstance(post_in, torch.Tensor) else [dup(t) for t in post_in]
-                lshape = self.posterior.latent_shapes(image.shape[1:4])
-                if eps_q is not None:
-                    eps1 = [e for e in eps_q]
-                elif getattr(self.posterior, "rng", None) is not None and _os.environ.get("M1_LATENT_RNG", "1") != "0":
-                    eps1 = None                     # the latent kernels draw for themselves (ops.latent_sample rng=...)
-                else:
-                    # ONE generator launch for the draws of all levels, in the activation storage type (views of one buffer)
-                    sizes = [B * int(np.prod(shp)) for shp in lshape]
-                    flat = torch.randn(sum(sizes), device=image.device, dtype=image.dtype)
-                    if _os.environ.get("M1_DEBUG_FIXED_EPS"):          # debug: one persistent draw instead of a generator launch per step
-                        if getattr(self, "_dbg_eps", None) is None:
-                            self._dbg_eps = flat.clone()
-                        flat = self._dbg_eps
-                    eps1, off = [], 0
-                    for n_, shp in zip(sizes, lshape):
-                        eps1.append(flat[off:off + n_].view(B, *shp)); off += n_
-                # The prior core reads the posterior's latents only in its latent decoder (dec_hi / sersp): its U-Net -- encoder,
-                # gates, nested decoder -- is independent of the posterior pass, which therefore runs on a side stream next to
-                # it (and so do their backward passes); the prior joins where it first reads a z.
-                img2 = image if share else dup(image)
-                post_kw = dict(prob_mean=False, prob_z_q=None, eps=eps1, mark=mq, need="latents", eps_first_half=True, dup_first=share)
-                if _PQ_LANES:
-                    with ops.branch(image.device, 8) as lane:
-                        q = self.posterior(post2, **post_kw)
-                    z_ready = lambda: lane.join(*q['prob_used_latents'], *q['prob_distributions'])
-                else:
-                    q, z_ready = self.posterior(post2, **post_kw), None
-                p = self.prior(img2, prob_mean=False, prob_z_q=q['prob_used_latents'], mark=mp, need="full", tail_from=B, z_ready=z_ready,
-                               dup_first=share)
-                train_conv = self.stitch(p['prob_decoder_features'])                                    # networks.py:356 (p_z_qm)
-                kl = None                                                                               # networks.py:373-385
-                for lvl, (qd, pd) in enumerate(zip(q['prob_distributions'], p['prob_distributions'])):
-                    k = ops.kl_mvn_diag(qd, pd, first=B)                                                # (q_sample, p_z_q): the first halves
-                    kl = k if kl is None else kl + k
-                    if lvl == 0 and mp is not None:
-                        mp("a", pd)          # the prior's coarsest latent head is reached through its KL term only
-                outputs['prob_train_conv'] = train_conv
-                outputs['prob_kl'] = kl
-                outputs['_q_latents'] = [z[:B] for z in q['prob_used_latents']]
-                outputs['prob_softmax'] = ops.softmax_heads([train_conv], [(1, 1, 1)])
-                outputs['_heads'], outputs['_ups'] = [train_conv], [(1, 1, 1)]
+            if train_outputs and self.stack_passes and not summarise:
+                outputs = self._stacked_training_passes(image, post_in, eps_q)
             elif train_outputs:
-                # (two lanes -- posterior mean -> prior -> logits next to posterior sample -> prior -> KL -- were measured: no gain,
-                # the full model is dominated by kernels that fill the GPU on their own; nested forks also break graph capture)
-                # every pass marks the nodes that close its exchange groups: a group is sent once ALL its marks of the step
-                # have fired, i.e. after the backward of the last pass through that core, whatever order autograd picks
-                mq, mp = self._marker("posterior."), self._marker("prior.")
-                # three of the four passes feed only latents / distributions into the outputs: they skip what nothing reads
-                # (M1Core.forward need="latents"; the first call prints the reference's full stage summary if asked to)
-                lat = "full" if (self.show_summary and not self._summarised) else "latents"
-                q_sample = self.posterior(post_in, prob_mean=False, prob_z_q=None, eps=eps_q, mark=mq, need=lat)   # networks.py:348
-                q_mean = self.posterior(post_in, prob_mean=True, prob_z_q=None, mark=mq, need=lat)                  # networks.py:349
-                p_z_q = self.prior(image, prob_mean=False, prob_z_q=q_sample['prob_used_latents'], mark=mp, need=lat)   # networks.py:351
-                p_z_qm = self.prior(image, prob_mean=False, prob_z_q=q_mean['prob_used_latents'], mark=mp)    # networks.py:352
-                train_conv = self.stitch(p_z_qm['prob_decoder_features'])                               # networks.py:356
-                kl = None                                                                               # networks.py:373-385
-                for lvl, (q, p) in enumerate(zip(q_sample['prob_distributions'], p_z_q['prob_distributions'])):
-                    k = ops.kl_mvn_diag(q, p)
-                    kl = k if kl is None else kl + k
-                    if lvl == 0 and mp is not None:
-                        mp("a", p)           # the prior's coarsest latent head is reached through its KL term only
-                outputs['prob_train_conv'] = train_conv
-                outputs['prob_kl'] = kl
-                outputs['_q_latents'] = q_sample['prob_used_latents']
-                # networks.py:388-390: with deep_supervision the concat partner y_softmax[..., nc:] is EMPTY
-                outputs['prob_softmax'] = ops.softmax_heads([train_conv], [(1, 1, 1)])
-                outputs['_heads'], outputs['_ups'] = [train_conv], [(1, 1, 1)]
+                # (the first call prints the reference's full stage summary if asked to: every pass then runs in full)
+                outputs = self._separate_training_passes(image, post_in, eps_q, "full" if summarise else "latents")
             if with_infer or not train_outputs:
-                p_sample = self.prior(image, prob_mean=False, prob_z_q=None, eps=eps_p)                 # networks.py:350
-                outputs['prob_infer_conv'] = self.stitch(p_sample['prob_decoder_features'])             # networks.py:355
-            if self.show_summary and not self._summarised:
-                print('-------------------------------------------------------------------------------------')
-                print('Hierarchical Prob. 3D U-Net (Type: M1) - Prior Network')
-                print('-------------------------------------------------------------------------------------')
-                self.prior.summary()
-                print('-------------------------------------------------------------------------------------')
-                print('Hierarchical Prob. 3D U-Net (Type: M1) - Posterior Network')
-                print('-------------------------------------------------------------------------------------')
-                self.posterior.summary()
-                print('-------------------------------------------------------------------------------------')
-                self._summarised = True
+                outputs['prob_infer_conv'] = self._inference_pass(image, eps_p)
+        if summarise:
+            self._print_summary()
+            self._summarised = True
         self.last = outputs
         return outputs
+
+    def _deterministic_pass(self, inputs):
+        o = self.core(inputs, prob_mean=False, prob_z_q=None, mark=self._marker("core."))   # networks.py:281 (+ App. C-1)
+        return {k: o[k] for k in ('y_softmax', 'logits', '_heads', '_ups')}
+
+    def _stacked_training_passes(self, image, post_in, eps_q):
+        """The four training passes (networks.py:348,349,351,352) as TWO, stacked along the batch axis: every op of the
+        model is per sample (InstanceNorm statistics, SE gate, dropout draw per element), so
+          posterior([x; x], eps = [eps; 0])        = [q_sample; q_mean]       (z = mu + sigma*0 = mu: the prob_mean pass)
+          prior([img; img], z = [z_sample; z_mean]) = [p_z_q; p_z_qm]
+        with half the launches at twice the batch (a 2-volume batch leaves the deep levels with 1,000-8,000 voxels per
+        launch).  Only p_z_qm needs the decoder features: the layers behind the latent heads run on the batch slice
+        [B:] (M1Core.forward tail_from); the posterior passes and p_z_q are latents-only (need="latents")."""
+        B = int(image.shape[0])
+        mq, mp = self._marker("posterior."), self._marker("prior.")
+        dup = lambda t: torch.cat([t, t], dim=0)
+        # both halves of a stacked pass read the SAME input: everything in front of the first dropout draw (stem + serse1 up to
+        # its last kernel) is one computation, run once on B samples (M1Core.forward dup_first; M1_DEDUP_PREFIX=0: stack the input)
+        vec = 8 if image.dtype == torch.bfloat16 else 4
+        share = (_os.environ.get("M1_DEDUP_PREFIX", "1") != "0" and all(
+            (not c.serse1.identity_residual) and c.serse1.filters % vec == 0 for c in (self.prior, self.posterior)))
+        if share:
+            post2 = post_in
+        else:
+            post2 = dup(post_in) if isinstance(post_in, torch.Tensor) else [dup(t) for t in post_in]
+        lshape = self.posterior.latent_shapes(image.shape[1:4])
+        if eps_q is not None:
+            eps1 = [e for e in eps_q]
+        elif getattr(self.posterior, "rng", None) is not None and _os.environ.get("M1_LATENT_RNG", "1") != "0":
+            eps1 = None                     # the latent kernels draw for themselves (ops.latent_sample rng=...)
+        else:
+            # ONE generator launch for the draws of all levels, in the activation storage type (views of one buffer)
+            sizes = [B * int(np.prod(shp)) for shp in lshape]
+            flat = torch.randn(sum(sizes), device=image.device, dtype=image.dtype)
+            eps1, off = [], 0
+            for n_, shp in zip(sizes, lshape):
+                eps1.append(flat[off:off + n_].view(B, *shp)); off += n_
+        # The prior core reads the posterior's latents only in its latent decoder (dec_hi / sersp): its U-Net -- encoder,
+        # gates, nested decoder -- is independent of the posterior pass, which therefore runs on a side stream next to
+        # it (and so do their backward passes); the prior joins where it first reads a z.
+        img2 = image if share else dup(image)
+        post_kw = dict(prob_mean=False, prob_z_q=None, eps=eps1, mark=mq, need="latents", eps_first_half=True, dup_first=share)
+        if _PQ_LANES:
+            with ops.branch(image.device, 8) as lane:
+                q = self.posterior(post2, **post_kw)
+            z_ready = lambda: lane.join(*q['prob_used_latents'], *q['prob_distributions'])
+        else:
+            q, z_ready = self.posterior(post2, **post_kw), None
+        p = self.prior(img2, prob_mean=False, prob_z_q=q['prob_used_latents'], mark=mp, need="full", tail_from=B, z_ready=z_ready,
+                       dup_first=share)
+        return self._training_outputs(q, p, p, mp, first=B)            # (q_sample, p_z_q): the first halves; p_z_qm: the second
+
+    def _separate_training_passes(self, image, post_in, eps_q, lat):
+        """The four training passes one after the other.  Three of them feed only latents / distributions into the outputs: with
+        ``lat="latents"`` they skip what nothing reads (M1Core.forward ``need``).
+        (two lanes -- posterior mean -> prior -> logits next to posterior sample -> prior -> KL -- were measured: no gain,
+        the full model is dominated by kernels that fill the GPU on their own; nested forks also break graph capture)"""
+        # every pass marks the nodes that close its exchange groups: a group is sent once ALL its marks of the step
+        # have fired, i.e. after the backward of the last pass through that core, whatever order autograd picks
+        mq, mp = self._marker("posterior."), self._marker("prior.")
+        q_sample = self.posterior(post_in, prob_mean=False, prob_z_q=None, eps=eps_q, mark=mq, need=lat)   # networks.py:348
+        q_mean = self.posterior(post_in, prob_mean=True, prob_z_q=None, mark=mq, need=lat)                  # networks.py:349
+        p_z_q = self.prior(image, prob_mean=False, prob_z_q=q_sample['prob_used_latents'], mark=mp, need=lat)   # networks.py:351
+        p_z_qm = self.prior(image, prob_mean=False, prob_z_q=q_mean['prob_used_latents'], mark=mp)    # networks.py:352
+        return self._training_outputs(q_sample, p_z_q, p_z_qm, mp)
+
+    def _training_outputs(self, q_sample, p_z_q, p_z_qm, mp, first=None):
+        """Train logits and KL(Q||P) from the posterior's sampling pass, the prior pass given its latents and the prior pass given the
+        posterior's mean.  ``first=B``: the passes are stacked and the first two are the first B samples of their batches."""
+        train_conv = self.stitch(p_z_qm['prob_decoder_features'])                               # networks.py:356
+        kl = None                                                                               # networks.py:373-385
+        for lvl, (qd, pd) in enumerate(zip(q_sample['prob_distributions'], p_z_q['prob_distributions'])):
+            k = ops.kl_mvn_diag(qd, pd, first=first)
+            kl = k if kl is None else kl + k
+            if lvl == 0 and mp is not None:
+                mp("a", pd)          # the prior's coarsest latent head is reached through its KL term only
+        zq = q_sample['prob_used_latents']
+        # networks.py:388-390: with deep_supervision the concat partner y_softmax[..., nc:] is EMPTY
+        return {'prob_train_conv': train_conv, 'prob_kl': kl, '_q_latents': zq if first is None else [z[:first] for z in zq],
+                'prob_softmax': ops.softmax_heads([train_conv], [(1, 1, 1)]), '_heads': [train_conv], '_ups': [(1, 1, 1)]}
+
+    def _inference_pass(self, image, eps_p):
+        p_sample = self.prior(image, prob_mean=False, prob_z_q=None, eps=eps_p)                 # networks.py:350
+        return self.stitch(p_sample['prob_decoder_features'])                                   # networks.py:355
+
+    def _print_summary(self):
+        bar = '-' * (85 if self.probabilistic else 68)
+        cores = ([('Hierarchical Prob. 3D U-Net (Type: M1) - Prior Network', self.prior),
+                  ('Hierarchical Prob. 3D U-Net (Type: M1) - Posterior Network', self.posterior)] if self.probabilistic
+                 else [('Deterministic 3D U-Net (Type: M1)', self.core)])
+        for title, core in cores:
+            print(bar); print(title); print(bar)
+            core.summary()
+        print(bar)
 
 
 def m1(inputs, num_classes,

@@ -217,6 +217,42 @@ def test_c1_probabilistic_other_latent_configurations(dev, latents, dense, seed)
     _check_grads(m, g64, orc[torch.float32][2])
 
 
+@pytest.mark.parametrize("latents,dense,seed", LATENT_CONFIGS)
+def test_latents_only_pass_equals_the_full_pass(dev, latents, dense, seed, monkeypatch):
+    """M1Core.forward(need="latents") evaluates only what the latent heads depend on -- decoder stages and latent-decoder levels
+    0 .. n_lat-2 -- and promises identical results: the layers it shares with the full pass run the same kernels on the same
+    inputs, so distributions and latents are bitwise equal, the decoder features are not returned, and the stage printout lacks
+    exactly the pruned stages (stage k: the gate att_conv{3-k}, the concat uconv{3-k}_ and, behind stage 0, its input uconv{4-k}).
+    The dropout-layer and latent-stream ids are counted per process: this model (no dropout, injected draws) takes its ids from copies
+    of the counters, so the models of the tests that run after this one draw what they drew before it existed."""
+    NB, NW = PKG.unets.network_blocks, PKG.unets.networks
+    monkeypatch.setattr(NB._DropoutBase, "_next_id", list(NB._DropoutBase._next_id))
+    monkeypatch.setattr(NW.M1Core, "_next_latent_id", list(NW.M1Core._next_latent_id))
+    cfg = O.M1Config(input_spatial_dims=(4, 32, 32), filters=C1_FILTERS, strides=C1_STRIDES, dense_skip=dense,
+                     deep_supervision=False, probabilistic=True, prob_latent_dims=latents)
+    m = build_m1(cfg, dev)
+    load_params_into(m, O.fixture_params(cfg, seed=seed))
+    image = rnd((1, 4, 32, 32, 2), seed + 100).to(dev)
+    eps = [rnd((1, *s), seed + 300 + i).to(dev) for i, s in enumerate(O.latent_shapes(cfg))]
+    core = m.m1_model.prior
+    with torch.no_grad():
+        full = core(image, eps=eps, need="full")
+        shapes_full = dict(core._shapes)
+        lat = core(image, eps=eps, need="latents")
+        shapes_lat = dict(core._shapes)
+    n_lat = sum(1 for d in latents if d != 0)
+    for key in ("prob_distributions", "prob_used_latents"):
+        assert len(full[key]) == len(lat[key]) == n_lat, key
+        for a, b in zip(full[key], lat[key]):
+            assert torch.equal(a, b), key
+    assert full["prob_decoder_features"] is not None and lat["prob_decoder_features"] is None
+    pruned = set()
+    for k in range(max(0, n_lat - 1), 4):
+        pruned |= {f"att_conv{3 - k}", f"uconv{3 - k}_"} | ({f"uconv{4 - k}"} if k > 0 else set())
+    assert set(shapes_full) - set(shapes_lat) == pruned and set(shapes_lat) <= set(shapes_full)
+    assert all(shapes_lat[k] == shapes_full[k] for k in shapes_lat)
+
+
 def _three_class_target(shape, seed):
     """One-hot (B,D,H,W,3): background, a ball, a second ball (the first wins where they overlap)."""
     B, D, H, W = shape

@@ -16,7 +16,7 @@ cut = rest.index("--") if "--" in rest else len(rest)
 ref_env = dict(kv.split("=", 1) for kv in rest[:cut])
 run_env = dict(kv.split("=", 1) for kv in rest[cut + 1:])
 tmp = tempfile.mkdtemp()
-BASE = {"M1_PQ_LANES": "0", "M1_STREAMS": "0", "M1_BENCH_HIST": "1", "M1_DEBUG_TRACE": "16384", "M1_DEBUG_FIXED_EPS": "1"}
+BASE = {"M1_PQ_LANES": "0", "M1_STREAMS": "0", "M1_BENCH_HIST": "1", "M1_DEBUG_TRACE": "16384"}
 PG = {"M1_BENCH_FORCE_DIST": "1", "M1_BENCH_NO_COLLECTIVES": "1"}
 steps = os.environ.get("STEPS", "2")
 
