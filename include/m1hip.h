@@ -446,6 +446,50 @@ enum m1_feed_mode { M1_FEED_TRAIN = 0, M1_FEED_VALID = 1, M1_FEED_TEST = 2 };
 int m1_label_prepare(const uint8_t* ann, const float* image, float* x_out, float* detection, float* kl, int B, int D, int H, int W,
                      int C, int objective, int mode, int probabilistic, const int* taps, void* stream);
 
+/* ---- scan preprocessing : tf2.5/scripts/preprocess.py (P:) 29-39 whitening, 42-49 center_crop, 74-98 resize_image_with_crop_or_pad
+ *      (csrc/preprocess.hip; resample_img, P:52-71, is SimpleITK's B-spline and is not built) ----
+ * Every entry point reads a raw source (B, d, h, w, C), channel-last, `src_dtype` M1_RAW_F32 or M1_RAW_I16 (the scans' native type;
+ * the load converts, every int16 is exact in fp32), through ONE index map, so that no cropped or padded intermediate volume exists.
+ * m1_crop_pad_t: src = (d, h, w), dst = the output extent, output voxel o of an axis reads source index o + start (start < 0 where the
+ * axis is padded in front).  An index outside [0, n) goes through `mode`: M1_PAD_CONSTANT -> the value cval, M1_PAD_EDGE -> the nearest
+ * voxel, M1_PAD_REFLECT -> period 2(n - 1) without repeating the edge (index 0 when n == 1), M1_PAD_SYMMETRIC -> period 2n with the edge
+ * repeated: np.pad's modes, its iterated reflection for pads wider than the axis included.  Every source index is clamped after the
+ * map: a wrong table cannot fault.  The axes are independent, which is what P:98 computes (it pads the cropped volume).
+ * The "output domain" of a (b, c) slice is its n = dst[0] * dst[1] * dst[2] output values, pad values included: all statistics are
+ * taken over it, which is what the reference gets when it whitens after cropping.  Non-finite input is outside the contract (the
+ * reference's own result for it is an accident of `image * 0.`): the selection orders NaNs by their bit patterns and the whitened
+ * output is then NaN.
+ * Common rules: B, C and every extent > 0 and pointers aligned to their element type, else M1_ERR_BAD_ARG; n >= 2^31, C > 8, nq > 4,
+ * a mode or dtype outside the enums: M1_ERR_UNSUPPORTED; both before any launch.  ws: m1_preprocess_ws_bytes bytes, 8-byte aligned
+ * (one buffer serves m1_order_stats and then m1_whiten of one batch); its contents need no initialisation.  No atomics on global
+ * memory, no memset / memcpy nodes, no host synchronisation; results are bit-identical run to run. */
+enum m1_raw_dtype { M1_RAW_F32 = 0, M1_RAW_I16 = 1 };
+enum m1_pad_mode { M1_PAD_CONSTANT = 0, M1_PAD_EDGE = 1, M1_PAD_REFLECT = 2, M1_PAD_SYMMETRIC = 3 };
+typedef struct { int src[3]; int dst[3]; int start[3]; int mode; float cval; } m1_crop_pad_t;
+/* pure host; nq = 0 sizes the buffer for m1_whiten alone.  0 for arguments the entry points would reject. */
+size_t m1_preprocess_ws_bytes(const m1_crop_pad_t* g, int B, int C, int nq);
+/* The gather alone: out (B, dst[0], dst[1], dst[2], C) fp32 or bf16 (out_dtype M1_F32 / M1_BF16) = the mapped source values.
+ * 16-byte stores when dst[2] * C is a multiple of 4 and out is aligned to 4 elements (vector loads for the runs that are contiguous
+ * and aligned in the source), element accesses otherwise. */
+int m1_crop_pad(const void* src, int src_dtype, const m1_crop_pad_t* g, int B, int C, void* out, int out_dtype, void* stream);
+/* Exact order statistics of every (b, c) slice's output domain.  Quantile j is given as ranks[j] in [0, n) and weights[j] in [0, 1]
+ * (HOST arrays of nq entries; numpy's linear rule in fp64: virtual = q / 100 * (n - 1), rank = floor, weight = fraction).  With a[]
+ * the sorted slice: pairs (B, C, nq, 2) fp32 = {a[rank], a[min(rank + 1, n - 1)]}, bit-exact (-0.0 and +0.0 are ordered by their
+ * sign bits); values (B, C, nq) fp32 = a[rank] + (a[rank + 1] - a[rank]) * weight evaluated in fp64 and rounded once.
+ * Method: radix select on the order-preserving 32-bit key of the fp32 value, four passes of 8 bits; the 2 nq ranks advance in the same
+ * passes and share a histogram while their prefixes agree.  Per pass one launch of per-block LDS histograms (integer LDS atomics:
+ * counts do not depend on order) and one launch that folds the blocks' histograms in ws and advances the prefixes: 8 launches. */
+int m1_order_stats(const void* src, int src_dtype, const m1_crop_pad_t* g, int B, int C, const int* ranks, const double* weights,
+                   int nq, float* pairs, float* values, void* ws, void* stream);
+/* Whitening (P:29-39) of every (b, c) slice's output domain: y = min(max(x, lo), hi) with {lo, hi} = bounds[b][c] when bounds
+ * ((B, C, 2) fp32, DEVICE: the `values` of m1_order_stats for the quantiles {100 - p, p}) is not NULL -- lo > hi yields hi everywhere,
+ * as np.clip does; mean and population standard deviation (ddof = 0) of y in fp64 (per-block {count, mean, M2} from two sweeps of
+ * the block's own chunk, merged in block order by Chan's rule: no sum of raw squares); stats (B, C, 2) fp64 = {mean, std}; then
+ * out (B, dst[0], dst[1], dst[2], C) fp32 or bf16 = (y - (float)mean) / (float)std in fp32 with IEEE division when (float)std > 0,
+ * +0.0 otherwise; the bf16 store is the round-to-nearest-even of that fp32 value (m1_cast's).  3 launches. */
+int m1_whiten(const void* src, int src_dtype, const m1_crop_pad_t* g, int B, int C, const float* bounds, void* out, int out_dtype,
+              double* stats, void* ws, void* stream);
+
 /* ---- MonteCarloDropout / Dropout : B:142-143 ; N:462-463 (Philox4x32-10, mask regenerated in bwd) ---- */
 int m1_dropout(const void* x, void* y, long long n, float rate, const uint64_t* rng, uint64_t layer_id, int dtype,
                void* stream);

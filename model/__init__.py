@@ -1,5 +1,5 @@
 """Reference-shaped import path: ``import model.unets as unets; import model.losses as losses`` (as in the
-reference's train_model.py:19-22, ``model.augmentations`` and ``model.data_generators`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
+reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators`` and ``model.preprocess`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
 import importlib
 import os
 import sys
@@ -14,6 +14,7 @@ initializers = _pkg.initializers
 optim = _pkg.optim
 augmentations = _pkg.augmentations
 data_generators = _pkg.data_generators
+preprocess = _pkg.preprocess
 sys.modules[__name__ + ".unets"] = unets
 sys.modules[__name__ + ".unets.networks"] = unets.networks
 sys.modules[__name__ + ".unets.network_blocks"] = unets.network_blocks
@@ -21,3 +22,4 @@ sys.modules[__name__ + ".unets.modelio"] = unets.modelio
 sys.modules[__name__ + ".losses"] = losses
 sys.modules[__name__ + ".augmentations"] = augmentations
 sys.modules[__name__ + ".data_generators"] = data_generators
+sys.modules[__name__ + ".preprocess"] = preprocess

@@ -65,6 +65,16 @@ M1_AUG_MASTER, M1_AUG_ZOOM, M1_AUG_FLIP, M1_AUG_ROTATE, M1_AUG_TRANSLATE = 1, 2,
 M1_AUG_CSHIFT, M1_AUG_GAMMA, M1_AUG_POOR, M1_AUG_NOISE = 32, 64, 128, 256
 
 
+class m1_crop_pad_t(C.Structure):
+    """The crop / pad index map of the preprocessing kernels (include/m1hip.h)."""
+    _fields_ = [("src", C.c_int * 3), ("dst", C.c_int * 3), ("start", C.c_int * 3), ("mode", C.c_int), ("cval", C.c_float)]
+
+
+# enum m1_raw_dtype / m1_pad_mode
+M1_RAW_F32, M1_RAW_I16 = 0, 1
+M1_PAD_CONSTANT, M1_PAD_EDGE, M1_PAD_REFLECT, M1_PAD_SYMMETRIC = 0, 1, 2, 3
+
+
 # enum m1_label_objective / m1_feed_mode
 M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
 M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
@@ -148,6 +158,10 @@ SIGNATURES = {
     "m1_aug_intensity": (_i, [_vp, _vp, _vp, _u64, _vp] + [_i] * 8 + [_vp, _vp]),
     "m1_contour_smooth_u8": (_i, [_vp, _vp, _vp, _ll, _i, _i, C.POINTER(_i), _i, _vp]),
     "m1_label_prepare": (_i, [_vp] * 5 + [_i] * 8 + [C.POINTER(_i), _vp]),
+    "m1_preprocess_ws_bytes": (_sz, [C.POINTER(m1_crop_pad_t), _i, _i, _i]),
+    "m1_crop_pad": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, _vp, _i, _vp]),
+    "m1_order_stats": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, C.POINTER(_i), C.POINTER(_d), _i, _vp, _vp, _vp, _vp]),
+    "m1_whiten": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "m1_dropout": (_i, [_vp, _vp, _ll, _f, _vp, _u64, _i, _vp]),
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),

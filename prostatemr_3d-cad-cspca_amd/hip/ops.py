@@ -1108,6 +1108,87 @@ def prepare_labels(ann: Optional[torch.Tensor], image: torch.Tensor, train_obj: 
 
 
 # ---------------------------------------------------------------------------------------------------------
+# scan preprocessing (preprocess.hip; preprocess.py is the public surface)
+# ---------------------------------------------------------------------------------------------------------
+PAD_MODES = {"constant": L.M1_PAD_CONSTANT, "edge": L.M1_PAD_EDGE, "reflect": L.M1_PAD_REFLECT, "symmetric": L.M1_PAD_SYMMETRIC}
+_RAW_DTYPES = {torch.float32: L.M1_RAW_F32, torch.int16: L.M1_RAW_I16}
+
+
+def _raw(src: torch.Tensor, what: str):
+    _req(src)
+    if src.dim() != 5 or src.dtype not in _RAW_DTYPES:
+        raise RuntimeError(f"{what}: a raw fp32 / int16 source (B,d,h,w,C) expected, got {src.dtype} {tuple(src.shape)}")
+    return int(src.shape[0]), int(src.shape[4]), _RAW_DTYPES[src.dtype]
+
+
+def crop_pad_geom(src_dims, dst, start, mode: str = "constant", cval: float = 0.0) -> L.m1_crop_pad_t:
+    """The m1_crop_pad_t of a (d,h,w) source: output voxel o of an axis reads source index o + start."""
+    if mode not in PAD_MODES:
+        raise NotImplementedError(f"pad mode {mode!r}: built are {sorted(PAD_MODES)}")
+    if len(dst) != 3 or len(start) != 3 or any(int(v) < 1 for v in dst):
+        raise RuntimeError(f"crop / pad geometry: three positive output extents and three starts expected, got {tuple(dst)}, {tuple(start)}")
+    g = L.m1_crop_pad_t()
+    g.src[:], g.dst[:], g.start[:] = [int(v) for v in src_dims], [int(v) for v in dst], [int(v) for v in start]
+    g.mode, g.cval = PAD_MODES[mode], float(cval)
+    return g
+
+
+def _out_dtype(dtype) -> int:
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"preprocessing output: float32 / bfloat16 only, got {dtype}")
+    return L.M1_F32 if dtype == torch.float32 else L.M1_BF16
+
+
+def _pp_ws(g, B: int, Cn: int, nq: int, device) -> torch.Tensor:
+    n = int(L.load().m1_preprocess_ws_bytes(C.byref(g), B, Cn, nq))
+    return torch.empty(max(n, 8) // 8, dtype=torch.float64, device=device)
+
+
+def crop_pad(src: torch.Tensor, dst, start, mode: str = "constant", cval: float = 0.0, dtype=torch.float32) -> torch.Tensor:
+    """m1_crop_pad: the crop / pad gather of a raw (B,d,h,w,C) fp32 / int16 source -> (B,*dst,C) in ``dtype``."""
+    B, Cn, raw = _raw(src, "crop_pad")
+    g = crop_pad_geom(src.shape[1:4], dst, start, mode, cval)
+    out = torch.empty((B, *[int(v) for v in dst], Cn), dtype=dtype, device=src.device)
+    L.check(L.load().m1_crop_pad(_p(src), raw, C.byref(g), B, Cn, _p(out), _out_dtype(dtype), _stream()), "m1_crop_pad")
+    return out
+
+
+def order_stats(src: torch.Tensor, dst, start, ranks, weights, mode: str = "constant", cval: float = 0.0):
+    """m1_order_stats over the output domain of every (b, c) slice: (pairs (B,C,nq,2) fp32 = the exact {a[rank], a[min(rank+1,n-1)]},
+    values (B,C,nq) fp32 = their fp64 interpolation by ``weights`` rounded once).  ``ranks`` / ``weights``: host sequences
+    (preprocess.percentile_rank)."""
+    B, Cn, raw = _raw(src, "order_stats")
+    g = crop_pad_geom(src.shape[1:4], dst, start, mode, cval)
+    nq = len(ranks)
+    if nq < 1 or len(weights) != nq:
+        raise RuntimeError("order_stats: one weight per rank and at least one rank expected")
+    pairs = torch.empty((B, Cn, nq, 2), dtype=torch.float32, device=src.device)
+    values = torch.empty((B, Cn, nq), dtype=torch.float32, device=src.device)
+    ws = _pp_ws(g, B, Cn, min(nq, 4), src.device)
+    L.check(L.load().m1_order_stats(_p(src), raw, C.byref(g), B, Cn, (C.c_int * nq)(*[int(k) for k in ranks]),
+                                    (C.c_double * nq)(*[float(w) for w in weights]), nq, _p(pairs), _p(values), _p(ws), _stream()),
+            "m1_order_stats")
+    return pairs, values
+
+
+def whiten(src: torch.Tensor, dst, start, mode: str = "constant", cval: float = 0.0, bounds: Optional[torch.Tensor] = None,
+           dtype=torch.float32):
+    """m1_whiten: every (b, c) slice of the cropped / padded source clipped to ``bounds`` ((B,C,2) fp32 {lo, hi} on the device, or
+    None) and standardised -> (out (B,*dst,C) in ``dtype``, stats (B,C,2) fp64 {mean, std})."""
+    B, Cn, raw = _raw(src, "whiten")
+    _req(bounds)
+    g = crop_pad_geom(src.shape[1:4], dst, start, mode, cval)
+    if bounds is not None and (bounds.dtype != torch.float32 or tuple(bounds.shape) != (B, Cn, 2)):
+        raise RuntimeError(f"whiten: bounds must be fp32 {(B, Cn, 2)}, got {bounds.dtype} {tuple(bounds.shape)}")
+    out = torch.empty((B, *[int(v) for v in dst], Cn), dtype=dtype, device=src.device)
+    stats = torch.empty((B, Cn, 2), dtype=torch.float64, device=src.device)
+    ws = _pp_ws(g, B, Cn, 0, src.device)
+    L.check(L.load().m1_whiten(_p(src), raw, C.byref(g), B, Cn, _p(bounds), _p(out), _out_dtype(dtype), _p(stats), _p(ws), _stream()),
+            "m1_whiten")
+    return out, stats
+
+
+# ---------------------------------------------------------------------------------------------------------
 # dropout (standalone), cast
 # ---------------------------------------------------------------------------------------------------------
 class _Dropout(torch.autograd.Function):
