@@ -447,7 +447,7 @@ int m1_label_prepare(const uint8_t* ann, const float* image, float* x_out, float
                      int C, int objective, int mode, int probabilistic, const int* taps, void* stream);
 
 /* ---- scan preprocessing : tf2.5/scripts/preprocess.py (P:) 29-39 whitening, 42-49 center_crop, 74-98 resize_image_with_crop_or_pad
- *      (csrc/preprocess.hip; resample_img, P:52-71, is SimpleITK's B-spline and is not built) ----
+ *      (csrc/preprocess.hip; resample_img, P:52-71, is the next section: a restatement pinned against scipy, not against ITK) ----
  * Every entry point reads a raw source (B, d, h, w, C), channel-last, `src_dtype` M1_RAW_F32 or M1_RAW_I16 (the scans' native type;
  * the load converts, every int16 is exact in fp32), through ONE index map, so that no cropped or padded intermediate volume exists.
  * m1_crop_pad_t: src = (d, h, w), dst = the output extent, output voxel o of an axis reads source index o + start (start < 0 where the
@@ -489,6 +489,34 @@ int m1_order_stats(const void* src, int src_dtype, const m1_crop_pad_t* g, int B
  * +0.0 otherwise; the bf16 store is the round-to-nearest-even of that fp32 value (m1_cast's).  3 launches. */
 int m1_whiten(const void* src, int src_dtype, const m1_crop_pad_t* g, int B, int C, const float* bounds, void* out, int out_dtype,
               double* stats, void* ws, void* stream);
+
+/* ---- resampling to a target spacing : P:52-71 resample_img (csrc/resample.hip) ----
+ * The reference resamples with SimpleITK's ResampleImageFilter on a grid that keeps origin and direction and uses the identity
+ * transform: the grid is axis-aligned and the operation separable.  m1_resample_t: src = (d, h, w), dst = the number of outputs per
+ * axis, output o of an axis reads the continuous source index x = (first + o) * step (fp64; step = out_spacing / spacing, first > 0
+ * where only a window of the resampled axis is wanted).  A voxel is inside when -0.5 <= x < n - 0.5 on every axis (ITK's
+ * IsInsideBuffer) and receives `defval` otherwise.
+ *   order 3: cubic B-spline.  One pass per axis in the order 2, 1, 0; a pass prefilters every whole line of its axis (pole sqrt(3) - 2,
+ *            gain 6, mirror boundary of period 2(n - 1); a line of one voxel is left as it is) and emits 4-tap sums at floor(x) - 1 ..
+ *            floor(x) + 2 through the mirror map.  fp32 values, fp64 coordinates.  The causal start of a line longer than 24 voxels is
+ *            the mirror sum truncated after 24 terms (at most 2.6e-14 of max|src| is dropped); shorter lines use its closed form.
+ *            This is the algorithm of Unser / Thevenaz that ITK's BSplineDecompositionImageFilter and scipy.ndimage descend from; the
+ *            tests pin it against scipy.ndimage (spline_filter + map_coordinates, mode 'mirror').  Parity with ITK itself is NOT
+ *            pinned: SimpleITK is not available where this is built.  src fp32 / int16 -> out fp32 (out_dtype M1_RAW_F32).
+ *            ws: m1_resample_ws_bytes = 4 * (roundup4(B*C*src[0]*src[1]*dst[2]) + B*C*src[0]*dst[1]*dst[2]) bytes, 16-byte aligned: the
+ *            volumes after the passes over axis 2 and axis 1; its contents need no initialisation.  3 launches.
+ *   order 0: nearest neighbour, source index floor(x + 0.5) (ITK's round half up).  One gather launch; out_dtype = src_dtype, defval
+ *            is converted to it; ws is not used (m1_resample_ws_bytes is 0, ws may be NULL).
+ * NULL or misaligned pointers, B, C or an extent <= 0, first < 0, a step that is not finite and positive: M1_ERR_BAD_ARG.  A dtype or
+ * order outside the above, C > 8, any volume (source, intermediate, output; times B*C) of 2^31 elements or more, first + dst > 2^30,
+ * and for order 3 a source axis longer than M1_RESAMPLE_MAX_LINE: M1_ERR_UNSUPPORTED.  Both before any launch.  No atomics on global
+ * memory, no memset / memcpy nodes, no host synchronisation; everything runs on `stream`; results are bit-identical run to run, and
+ * an output does not depend on which window it is computed in. */
+#define M1_RESAMPLE_MAX_LINE 1024
+typedef struct { int src[3]; int dst[3]; int first[3]; int order; double step[3]; float defval; int _pad; } m1_resample_t;
+/* pure host.  0 for arguments m1_resample would reject, and for order 0. */
+size_t m1_resample_ws_bytes(const m1_resample_t* g, int B, int C);
+int m1_resample(const void* src, int src_dtype, const m1_resample_t* g, int B, int C, void* out, int out_dtype, void* ws, void* stream);
 
 /* ---- MonteCarloDropout / Dropout : B:142-143 ; N:462-463 (Philox4x32-10, mask regenerated in bwd) ---- */
 int m1_dropout(const void* x, void* y, long long n, float rate, const uint64_t* rng, uint64_t layer_id, int dtype,

@@ -75,6 +75,14 @@ M1_RAW_F32, M1_RAW_I16 = 0, 1
 M1_PAD_CONSTANT, M1_PAD_EDGE, M1_PAD_REFLECT, M1_PAD_SYMMETRIC = 0, 1, 2, 3
 
 
+class m1_resample_t(C.Structure):
+    """The axis-aligned resampling grid of m1_resample (include/m1hip.h)."""
+    _fields_ = [("src", C.c_int * 3), ("dst", C.c_int * 3), ("first", C.c_int * 3), ("order", C.c_int), ("step", C.c_double * 3),
+                ("defval", C.c_float), ("_pad", C.c_int)]
+
+
+M1_RESAMPLE_MAX_LINE = 1024
+
 # enum m1_label_objective / m1_feed_mode
 M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
 M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
@@ -162,6 +170,8 @@ SIGNATURES = {
     "m1_crop_pad": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, _vp, _i, _vp]),
     "m1_order_stats": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, C.POINTER(_i), C.POINTER(_d), _i, _vp, _vp, _vp, _vp]),
     "m1_whiten": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "m1_resample_ws_bytes": (_sz, [C.POINTER(m1_resample_t), _i, _i]),
+    "m1_resample": (_i, [_vp, _i, C.POINTER(m1_resample_t), _i, _i, _vp, _i, _vp, _vp]),
     "m1_dropout": (_i, [_vp, _vp, _ll, _f, _vp, _u64, _i, _vp]),
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),

@@ -1108,7 +1108,7 @@ def prepare_labels(ann: Optional[torch.Tensor], image: torch.Tensor, train_obj: 
 
 
 # ---------------------------------------------------------------------------------------------------------
-# scan preprocessing (preprocess.hip; preprocess.py is the public surface)
+# scan preprocessing (preprocess.hip, resample.hip; preprocess.py is the public surface)
 # ---------------------------------------------------------------------------------------------------------
 PAD_MODES = {"constant": L.M1_PAD_CONSTANT, "edge": L.M1_PAD_EDGE, "reflect": L.M1_PAD_REFLECT, "symmetric": L.M1_PAD_SYMMETRIC}
 _RAW_DTYPES = {torch.float32: L.M1_RAW_F32, torch.int16: L.M1_RAW_I16}
@@ -1186,6 +1186,39 @@ def whiten(src: torch.Tensor, dst, start, mode: str = "constant", cval: float = 
     L.check(L.load().m1_whiten(_p(src), raw, C.byref(g), B, Cn, _p(bounds), _p(out), _out_dtype(dtype), _p(stats), _p(ws), _stream()),
             "m1_whiten")
     return out, stats
+
+
+def resample_geom(src_dims, step, dst, first=(0, 0, 0), order: int = 3, default_value: float = 0.0) -> L.m1_resample_t:
+    """The m1_resample_t of a (d,h,w) source: output o of an axis reads the continuous source index (first + o) * step."""
+    if len(step) != 3 or len(dst) != 3 or len(first) != 3 or any(int(v) < 1 for v in dst):
+        raise RuntimeError(f"resampling geometry: three steps, three positive output extents and three firsts expected, got "
+                           f"{tuple(step)}, {tuple(dst)}, {tuple(first)}")
+    if order not in (0, 3):
+        raise NotImplementedError(f"resample: order {order!r} is not built; 0 (nearest) and 3 (cubic B-spline) are")
+    g = L.m1_resample_t()
+    g.src[:], g.dst[:], g.first[:] = [int(v) for v in src_dims], [int(v) for v in dst], [int(v) for v in first]
+    g.step[:] = [float(v) for v in step]
+    g.order, g.defval = int(order), float(default_value)
+    return g
+
+
+def resample(src: torch.Tensor, step, dst=None, first=(0, 0, 0), order: int = 3, default_value: float = 0.0) -> torch.Tensor:
+    """m1_resample: a raw (B,d,h,w,C) fp32 / int16 source on the grid whose output o of an axis reads the continuous source index
+    (first + o) * step -> (B,*dst,C), fp32 for order 3 (cubic B-spline), the source's dtype for order 0 (nearest neighbour).  ``step``
+    is three numbers (out_spacing / spacing per axis) with ``dst`` / ``first``, or a ready m1_resample_t."""
+    B, Cn, raw = _raw(src, "resample")
+    g = step if isinstance(step, L.m1_resample_t) else resample_geom(src.shape[1:4], step, dst, first, order, default_value)
+    if tuple(g.src) != tuple(int(v) for v in src.shape[1:4]):
+        raise RuntimeError(f"resample: the geometry is for a source {tuple(g.src)}, got {tuple(src.shape[1:4])}")
+    lib = L.load()
+    cubic = g.order == 3
+    out = torch.empty((B, *[int(v) for v in g.dst], Cn), dtype=torch.float32 if cubic else src.dtype, device=src.device)
+    ws, odt = None, raw                                 # (order 0 keeps the type and needs no workspace)
+    if cubic:
+        odt = _out_dtype(out.dtype)                     # (M1_F32 and M1_RAW_F32 are the same value)
+        ws = torch.empty(max(int(lib.m1_resample_ws_bytes(C.byref(g), B, Cn)), 16) // 4, dtype=torch.float32, device=src.device)
+    L.check(lib.m1_resample(_p(src), raw, C.byref(g), B, Cn, _p(out), odt, _p(ws), _stream()), "m1_resample")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -6,7 +6,11 @@ and ``predict`` / ``predict_mc``:
   * ``center_crop(img, cropz, cropx, cropy, center_2d_coords=None, multi_channel=False)`` (P:42-49);
   * ``resize_image_with_crop_or_pad(image, img_size, **kwargs)`` (P:74-98): per axis, pad (target - size) // 2 in front and the rest
     behind, or crop from floor((size - target) / 2); ``kwargs`` are np.pad's ``mode`` and a scalar ``constant_values``;
-  * ``resample_img`` (P:52-71) is SimpleITK's B-spline resampler and is not built.
+  * ``resample_img`` (P:52-71) takes an ITK image and still raises; its numerical content is ``resample(image, spacing, out_spacing,
+    is_label)`` on a plain array: the grid of P:52-71 keeps origin and direction and uses the identity transform, so it is axis-aligned,
+    output index j of an axis reads the continuous source index j * out_spacing / spacing, and the output size per axis is
+    round(size * spacing / out_spacing).  Images use a cubic B-spline, labels nearest neighbour.  Spacings are in array-axis order
+    (z, x, y), like the shapes, not in ITK's reversed order.
 
 A numpy array is processed on the host with numpy only (``whitening`` by the reference's own numpy calls; ``whitening_host`` /
 ``crop_pad_host`` are the restatement the tests measure the kernels against, pinned against a direct numpy computation, not against
@@ -16,6 +20,19 @@ csrc/preprocess.hip and returns a device tensor; there the results are fp32 (eve
 ``prepare_input`` is what the kernels were fused for: raw (B,d,h,w,C) fp32 / int16 on the device -> the whitened, cropped / padded
 (B,*img_size,C) network input in the model's storage type, every (sample, channel) on its own, with no host synchronisation and no
 cropped intermediate volume: the statistics and the element pass read the source through the crop / pad index map.
+
+``resample_host`` is the restatement of the resampler: Unser's recursive prefilter (pole sqrt(3) - 2, gain 6, mirror boundary of period
+2(n - 1), the causal start as the exact mirror sum) and the 4-tap cubic B-spline sum, axis after axis in the order RESAMPLE_AXIS_ORDER =
+(2, 1, 0), which is also the order of the kernels in csrc/resample.hip.  It is pinned against scipy.ndimage (``spline_filter(order=3,
+mode='mirror')`` + ``map_coordinates(order=3, mode='mirror', prefilter=False)``), which implements the same algorithm ITK's
+BSplineDecompositionImageFilter / BSplineInterpolateImageFunction descend from.  Parity with ITK itself is NOT pinned: SimpleITK is not
+installed where this is built.  One known difference: ITK truncates the causal start's sum at a horizon of 1e-10, the restatement (like
+scipy) sums it exactly, the kernels truncate it at 24 terms (2.6e-14): at most 1e-10 relative.  ``prepare_scan`` chains the resampler
+and ``prepare_input`` on the device and resamples only the part of the grid the crop keeps.
+
+Differences from the reference's resample_img, on purpose: the default pixel value is a parameter that defaults to 0 (P:66 passes
+GetPixelIDValue(), the pixel-TYPE enum, by accident); image results are fp32 (ITK casts back to the input pixel type); direction and
+origin do not enter, because P:63-64 keep both.
 
 Differences from the reference, on purpose: a ``center_crop`` window that leaves the volume raises ValueError (Python's negative-slice
 wrap at P:48-49 is an accident); pad modes other than constant / edge / reflect / symmetric raise NotImplementedError; non-finite
@@ -199,8 +216,159 @@ def resize_image_with_crop_or_pad(image, img_size=(64, 64, 64), **kwargs):
 
 
 def resample_img(itk_image, out_spacing=(2.0, 2.0, 2.0), is_label=False):
-    raise NotImplementedError("resample_img (P:52-71) is SimpleITK's ResampleImageFilter (B-spline / nearest neighbour on an ITK image): "
-                              "it is not built here; resample with SimpleITK and hand the array to prepare_input")
+    raise NotImplementedError("resample_img (P:52-71) takes a SimpleITK image, and SimpleITK is not a dependency of this package: hand "
+                              "the array and its spacing, both in (z, x, y) order, to resample(image, spacing, out_spacing, is_label), "
+                              "or the raw batch to prepare_scan")
+
+
+# ---- resampling to a target spacing (P:52-71) ----------------------------------------------------------------------------------
+BSPLINE_POLE = math.sqrt(3.0) - 2.0
+RESAMPLE_AXIS_ORDER = (2, 1, 0)
+
+
+def resample_size(shape, spacing, out_spacing) -> Tuple[int, ...]:
+    """P:56-58 per axis: int(np.round(n * (spacing / out_spacing))), np.round's half-to-even included."""
+    if not (len(shape) == len(spacing) == len(out_spacing)):
+        raise ValueError(f"resample_size: one spacing and one target spacing per axis expected, got {tuple(shape)}, {tuple(spacing)}, "
+                         f"{tuple(out_spacing)}")
+    size = tuple(int(np.round(int(n) * (float(s) / float(o)))) for n, s, o in zip(shape, spacing, out_spacing))
+    if any(v < 1 for v in size):
+        raise ValueError(f"resample_size: {tuple(shape)} at spacing {tuple(spacing)} has no voxel at spacing {tuple(out_spacing)}: {size}")
+    return size
+
+
+def resample_steps(spacing, out_spacing) -> Tuple[float, ...]:
+    """The continuous source index per output index of every axis, out_spacing / spacing in fp64."""
+    steps = tuple(float(o) / float(s) if float(s) > 0.0 else math.nan for s, o in zip(spacing, out_spacing))
+    if len(steps) != 3 or not all(math.isfinite(v) and v > 0.0 for v in steps):
+        raise ValueError(f"resample: three positive spacings and target spacings expected, got {tuple(spacing)}, {tuple(out_spacing)}")
+    return steps
+
+
+def _resample_window(shape, spacing, out_spacing, window):
+    size = resample_size(shape, spacing, out_spacing)
+    if window is None:
+        return size, tuple((0, n) for n in size)
+    window = tuple((int(f), int(c)) for f, c in window)
+    if len(window) != 3 or any(f < 0 or c < 1 or f + c > n for (f, c), n in zip(window, size)):
+        raise ValueError(f"resample: the window {window} leaves the resampled extent {size}")
+    return size, window
+
+
+def mirror_index(i, n: int):
+    """Source index of the mirror boundary (period 2(n - 1), the edge not repeated) for any integer array i; 0 when n == 1."""
+    i = np.asarray(i, dtype=np.int64)
+    if n == 1:
+        return np.zeros_like(i)
+    r = np.mod(i, 2 * (n - 1))
+    return np.where(r < n, r, 2 * (n - 1) - r)
+
+
+def bspline_prefilter_host(c: np.ndarray, axis: int, dtype=np.float64) -> np.ndarray:
+    """The cubic B-spline coefficients of the lines of ``c`` along ``axis`` in ``dtype`` values: gain (1 - z)(1 - 1/z), causal start
+    = the exact mirror sum (c[0] + z^(n-1) c[n-1] + sum_i z^i (c[i] + z^(n-1) c[n-1-i])) / (1 - z^(2n-2)), c+[k] = gain * s[k] + z *
+    c+[k-1], anticausal start z / (z^2 - 1) * (z * c+[n-2] + c+[n-1]), c[k] = z * (c[k+1] - c+[k]).  A line of one voxel is kept."""
+    c = np.moveaxis(np.asarray(c, dtype=dtype), axis, 0).copy()
+    n = c.shape[0]
+    if n < 2:
+        return np.moveaxis(c, 0, axis)
+    z = dtype(BSPLINE_POLE)
+    gain = (dtype(1) - z) * (dtype(1) - dtype(1) / z)
+    zn = z
+    for _ in range(2, n):
+        zn = zn * z
+    acc = c[0] + zn * c[n - 1]
+    zi = z
+    for i in range(1, n - 1):
+        acc = acc + zi * (c[i] + zn * c[n - 1 - i])
+        zi = zi * z
+    acc = acc / (dtype(1) - zn * zn)
+    acc = acc * gain
+    c[0] = acc
+    for k in range(1, n):
+        acc = gain * c[k] + z * acc
+        c[k] = acc
+    acc = (z * c[n - 2] + acc) * (z / (z * z - dtype(1)))
+    c[n - 1] = acc
+    for k in range(n - 2, -1, -1):
+        acc = z * (acc - c[k])
+        c[k] = acc
+    return np.moveaxis(c, 0, axis)
+
+
+def resample_coords(n: int, step: float, first: int, count: int):
+    """(x, inside) of the outputs first .. first + count - 1 of an axis of n voxels: x = j * step in fp64, inside = -0.5 <= x < n - 0.5
+    (ITK's IsInsideBuffer)."""
+    x = np.arange(first, first + count, dtype=np.float64) * np.float64(step)
+    return x, (x >= -0.5) & (x < n - 0.5)
+
+
+def _bspline_axis_host(c: np.ndarray, axis: int, x: np.ndarray, dtype) -> np.ndarray:
+    """The 4-tap cubic B-spline sum of the coefficient lines along ``axis`` at the coordinates x (fp64; floor and fraction in fp64,
+    weights and sums in ``dtype``)."""
+    n = c.shape[axis]
+    fl = np.floor(x)
+    y = (x - fl).astype(dtype)
+    zc = dtype(1) - y
+    w = (zc * zc * zc / dtype(6), (y * y * (y - dtype(2)) * dtype(3) + dtype(4)) / dtype(6),
+         (zc * zc * (zc - dtype(2)) * dtype(3) + dtype(4)) / dtype(6), y * y * y / dtype(6))
+    shape = [1] * c.ndim
+    shape[axis] = x.size
+    i = fl.astype(np.int64)
+    t = [np.take(c, mirror_index(i - 1 + k, n), axis=axis) * w[k].reshape(shape) for k in range(4)]
+    return ((t[0] + t[1]) + t[2]) + t[3]
+
+
+def resample_host(image: np.ndarray, spacing, out_spacing=(2.0, 2.0, 2.0), is_label=False, default_value=0, dtype=np.float64,
+                  window=None) -> np.ndarray:
+    """The restatement of P:52-71 the tests measure against, on a (z,x,y[,c]) array, in ``dtype`` values (the input is rounded to fp32
+    first).  Cubic path: for the axes 2, 1, 0 in turn, prefilter the lines of the axis and take the 4-tap sums at x_j = j * (out_spacing
+    / spacing); voxels outside on any axis are ``default_value``.  Nearest path (``is_label``): a gather at floor(x + 0.5), dtype kept.
+    ``window`` = ((first, count),) * 3 returns those output indices only."""
+    image = np.asarray(image)
+    if image.ndim not in (3, 4):
+        raise ValueError(f"resample: a (z,x,y[,c]) array expected, got shape {tuple(image.shape)}")
+    steps = resample_steps(spacing, out_spacing)
+    _, window = _resample_window(image.shape[:3], spacing, out_spacing, window)
+    coords = [resample_coords(image.shape[a], steps[a], *window[a]) for a in range(3)]
+    inside = np.ones((), dtype=bool)
+    for a, (_, ok) in enumerate(coords):
+        shape = [1] * image.ndim
+        shape[a] = ok.size
+        inside = inside & ok.reshape(shape)
+    if is_label:
+        out = image
+        for a, (x, ok) in enumerate(coords):
+            idx = np.clip(np.floor(np.where(ok, x, 0.0) + 0.5).astype(np.int64), 0, image.shape[a] - 1)
+            out = np.take(out, idx, axis=a)
+        return np.ascontiguousarray(np.where(inside, out, np.asarray(default_value).astype(image.dtype)).astype(image.dtype))
+    out = image.astype(np.float32).astype(dtype)
+    for a in RESAMPLE_AXIS_ORDER:
+        x, ok = coords[a]
+        out = _bspline_axis_host(bspline_prefilter_host(out, a, dtype), a, np.where(ok, x, 0.0), dtype)
+    return np.ascontiguousarray(np.where(inside, out, dtype(default_value)))
+
+
+def _resample_device(src: torch.Tensor, spacing, out_spacing, is_label, default_value, window=None) -> torch.Tensor:
+    steps = resample_steps(spacing, out_spacing)
+    _, window = _resample_window(src.shape[1:4], spacing, out_spacing, window)
+    return ops.resample(src, steps, [c for _, c in window], [f for f, _ in window], 0 if is_label else 3, float(default_value))
+
+
+def resample(image, spacing, out_spacing=(2.0, 2.0, 2.0), is_label=False, default_value=0):
+    """P:52-71 on a (z,x,y[,c]) array: numpy in -> the host path (fp64 compute, fp32 result for images, dtype kept for labels); device
+    tensor in -> the kernels of csrc/resample.hip (fp32 out for images, the input's dtype for labels)."""
+    if image.ndim not in (3, 4):
+        raise ValueError(f"resample: a (z,x,y[,c]) array expected, got shape {tuple(image.shape)}")
+    if not isinstance(image, torch.Tensor):
+        out = resample_host(image, spacing, out_spacing, is_label, default_value, np.float64)
+        return out if is_label else out.astype(np.float32)
+    src = image
+    if is_label and image.dtype not in (torch.float32, torch.int16):
+        src = image.to(torch.int16)                       # (uint8 and the other label types: every class index is exact in int16)
+    out = _resample_device(_five(src, image.ndim == 4), spacing, out_spacing, is_label, default_value)
+    out = out[0] if image.ndim == 4 else out[0, ..., 0]
+    return out.to(image.dtype) if is_label else out
 
 
 # ---- the fused call ----------------------------------------------------------------------------------------------------------
@@ -234,3 +402,27 @@ def prepare_input(raw: torch.Tensor, img_size, percentile=None, pad_mode="consta
     if raw.dtype not in (torch.float32, torch.int16):
         raw = raw.to(torch.float32)
     return _whiten_device(raw.contiguous(), tuple(int(v) for v in img_size), start, mode, float(cval), percentile, dtype)
+
+
+def scan_window(shape, spacing, out_spacing, img_size):
+    """((first, count),) * 3 of the resampled grid that resize_image_with_crop_or_pad to ``img_size`` keeps: the crop window where the
+    resampled size exceeds the target, the whole axis otherwise."""
+    size = resample_size(shape, spacing, out_spacing)
+    return tuple(((n - int(t)) // 2, int(t)) if n > int(t) else (0, n) for n, t in zip(size, img_size))
+
+
+def prepare_scan(raw: torch.Tensor, spacing, out_spacing, img_size, percentile=None, pad_mode="constant", constant_values=0,
+                 dtype=torch.float32, default_value=0):
+    """raw (B,d,h,w,C) fp32 / int16 on the device at ``spacing`` -> what prepare_input(resample(raw), img_size, ...) returns, bit for
+    bit: the cubic B-spline resampling to ``out_spacing`` of only the part of the grid the crop keeps (``scan_window``; an output does
+    not depend on the window it is computed in), then prepare_input on it, which pads the axes that are still short.  3 launches more
+    than prepare_input; nothing synchronises, so the call can be captured."""
+    if not isinstance(raw, torch.Tensor) or raw.dim() != 5:
+        raise ValueError("prepare_scan: a device tensor (B,d,h,w,C) expected")
+    if len(img_size) != 3:
+        raise ValueError(f"prepare_scan: three target sizes expected, got {tuple(img_size)}")
+    if raw.dtype not in (torch.float32, torch.int16):
+        raw = raw.to(torch.float32)
+    window = scan_window(raw.shape[1:4], spacing, out_spacing, img_size)
+    vol = _resample_device(raw.contiguous(), spacing, out_spacing, False, default_value, window)
+    return prepare_input(vol, img_size, percentile=percentile, pad_mode=pad_mode, constant_values=constant_values, dtype=dtype)
