@@ -518,6 +518,72 @@ typedef struct { int src[3]; int dst[3]; int first[3]; int order; double step[3]
 size_t m1_resample_ws_bytes(const m1_resample_t* g, int B, int C);
 int m1_resample(const void* src, int src_dtype, const m1_resample_t* g, int B, int C, void* out, int out_dtype, void* ws, void* stream);
 
+/* ---- connected components, lesion candidates and matching : train_model.py's `regionprops` import, callbacks.py's `compute_FROC`
+ *      (csrc/components.hip; detection.py is the public surface.  The reference ships neither function: the numbering is pinned
+ *      against scipy.ndimage.label, the extraction and matching rules are this project's own) ----
+ * Volumes are (B, D, H, W) with one value per voxel, n = D * H * W.  Common rules: NULL or misaligned pointers, B or an extent <= 0,
+ * connectivity outside 1..3, max_components / max_candidates <= 0, max_a / max_b < 0: M1_ERR_BAD_ARG; B > 65535, B * n >= 2^31 - 1, a table of 2^31 cells or more, a dtype outside the
+ * enum: M1_ERR_UNSUPPORTED; both before any launch.  Only integer atomics (min, max, add) touch global memory: results are bit-identical
+ * run to run.  No kernel waits for another workgroup; zero fills are kernels (no memset / memcpy nodes); nothing synchronises.
+ * m1_cc_label: foreground = src > threshold (strict; fp32 or uint8 source, the uint8 converted to fp32; NaN is background), the
+ *   threshold being threshold_dev[b] (DEVICE, B floats) when threshold_dev is not NULL and `threshold` otherwise.  connectivity 1 / 2 / 3
+ *   = the 6- / 18- / 26-neighbourhood (scipy.ndimage.generate_binary_structure(3, c)); no neighbour across a row end, a slice end or a
+ *   batch entry.  labels (B, D, H, W) int32: 0 = background, components 1..K_b numbered per batch entry in raster order of each
+ *   component's first voxel (scipy.ndimage.label's numbering); counts (B) int32 = K_b.  There is no cap on K_b.
+ *   ws: m1_cc_ws_bytes(B, D, H, W) bytes, 16-byte aligned, contents need no initialisation.  6 launches: union-find in LDS per
+ *   M1_CC_TILE_Z x _Y x _X tile, atomicMin unions across tile borders, flatten into a second buffer, ranks of the roots by a block scan
+ *   plus a fixed-order fold of the block totals.
+ * m1_cc_stats: rows (B, max_components) of m1_cc_row_t, row l - 1 of a batch entry for its label l <= max_components (larger labels get
+ *   no row; rows above K_b are all zero).  values (fp32, same shape) may be NULL: vmax is then 0 and argmax the component's first voxel.
+ *   argmax: linear index inside the batch entry of the largest value (-0.0 counts as +0.0), ties to the smallest index; lo / hi: bounding
+ *   box per axis (z, y, x), hi exclusive as scipy.ndimage.find_objects; sum: coordinate sums (centroid = sum / count).  3 launches.
+ * m1_cc_overlap: table (B, max_a + 1, max_b + 1) int32, table[b][i][j] = voxels with a == i and b == j (row / column 0: background); a
+ *   voxel whose label is negative or above its cap is counted nowhere.  2 launches.
+ * One round of the dynamic extraction (detection.extract_lesion_candidates), for every batch entry at once, its state in DEVICE memory:
+ *   state = 8 * B 4-byte words, word k of sample b at state[k * B + b], k = enum m1_cc_state.
+ *   m1_cc_peak: PEAK / ARGMAX = the maximum of w (B, n) fp32 and its index (ties to the smallest), THRESHOLD = PEAK / factor (fp32, IEEE
+ *     division), SEL = COUNT = 0; reset != 0 first clears DONE and NCAND; then DONE = 1 where not PEAK > min_confidence.  Per-block
+ *     partial maxima in ws (the front of a m1_cc_ws_bytes buffer) folded in block order.  2 launches.
+ *   m1_cc_select: SEL = labels[b][ARGMAX] and COUNT = its voxels; 0 / 0 for a sample that is DONE; a SEL of 0 (the peak is background
+ *     under its own threshold) sets DONE.  2 launches.
+ *   m1_cc_take: where labels == SEL != 0: w = 0 always, and when COUNT >= min_voxels and NCAND < max_candidates: detection_map = PEAK,
+ *     candidates = NCAND + 1; then confidences[b][NCAND] = PEAK and NCAND += 1.  reset != 0: every other element of detection_map
+ *     (B, n) fp32, candidates (B, n) int32 and confidences (B, max_candidates) fp32 is written as 0 and NCAND starts at 0 -- the first
+ *     round initialises the outputs; with w_src (B, n) not NULL it also initialises w = w_src outside the taken component (the
+ *     round's peak and labels were then computed from w_src: no copy of the probability map is made beforehand).  2 launches.
+ * m1_cc_relabel: the candidates of a FIXED threshold from the rows of m1_cc_stats: components with count >= min_voxels keep their order
+ *   and become candidates 1..ncand[b]; map (B, max_components) int32 = candidate number of each row or 0, confidences
+ *   (B, max_components) fp32 = vmax per candidate then zeros, candidates / detection_map (B, n) = the number / vmax on the kept
+ *   components' voxels and 0 elsewhere.  2 launches. */
+#define M1_CC_TILE_Z 4
+#define M1_CC_TILE_Y 8
+#define M1_CC_TILE_X 32
+enum m1_cc_dtype { M1_CC_F32 = 0, M1_CC_U8 = 1 };
+enum m1_cc_state {
+    M1_CC_ST_PEAK = 0, M1_CC_ST_ARGMAX = 1, M1_CC_ST_THRESHOLD = 2, M1_CC_ST_SEL = 3, M1_CC_ST_COUNT = 4, M1_CC_ST_DONE = 5,
+    M1_CC_ST_NCAND = 6, M1_CC_ST_SPARE = 7
+};
+typedef struct {
+    int32_t count;
+    float vmax;
+    int64_t argmax;
+    int32_t lo[3];
+    int32_t hi[3];
+    int64_t sum[3];
+} m1_cc_row_t; /* 64 bytes */
+/* pure host.  0 for arguments m1_cc_label would reject. */
+size_t m1_cc_ws_bytes(int B, int D, int H, int W);
+int m1_cc_label(const void* src, int src_dtype, float threshold, const float* threshold_dev, int connectivity, int B, int D, int H, int W,
+                int* labels, int* counts, void* ws, void* stream);
+int m1_cc_stats(const int* labels, const float* values, int B, int D, int H, int W, int max_components, m1_cc_row_t* rows, void* stream);
+int m1_cc_overlap(const int* a, const int* b, int B, long long n, int max_a, int max_b, int* table, void* stream);
+int m1_cc_peak(const float* w, int B, long long n, float factor, float min_confidence, int reset, int* state, void* ws, void* stream);
+int m1_cc_select(const int* labels, int B, long long n, int* state, void* stream);
+int m1_cc_take(const int* labels, int* state, const float* w_src, float* w, float* detection_map, int* candidates, float* confidences, int B, long long n,
+               int max_candidates, int min_voxels, int reset, void* stream);
+int m1_cc_relabel(const int* labels, const m1_cc_row_t* rows, int B, long long n, int max_components, int min_voxels, int* map,
+                  float* detection_map, int* candidates, float* confidences, int* ncand, void* stream);
+
 /* ---- MonteCarloDropout / Dropout : B:142-143 ; N:462-463 (Philox4x32-10, mask regenerated in bwd) ---- */
 int m1_dropout(const void* x, void* y, long long n, float rate, const uint64_t* rng, uint64_t layer_id, int dtype,
                void* stream);

@@ -1,5 +1,5 @@
 """Reference-shaped import path: ``import model.unets as unets; import model.losses as losses`` (as in the
-reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators`` and ``model.preprocess`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
+reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators``, ``model.preprocess`` and ``model.detection`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
 import importlib
 import os
 import sys
@@ -15,6 +15,7 @@ optim = _pkg.optim
 augmentations = _pkg.augmentations
 data_generators = _pkg.data_generators
 preprocess = _pkg.preprocess
+detection = _pkg.detection
 sys.modules[__name__ + ".unets"] = unets
 sys.modules[__name__ + ".unets.networks"] = unets.networks
 sys.modules[__name__ + ".unets.network_blocks"] = unets.network_blocks
@@ -23,3 +24,4 @@ sys.modules[__name__ + ".losses"] = losses
 sys.modules[__name__ + ".augmentations"] = augmentations
 sys.modules[__name__ + ".data_generators"] = data_generators
 sys.modules[__name__ + ".preprocess"] = preprocess
+sys.modules[__name__ + ".detection"] = detection

@@ -83,6 +83,18 @@ class m1_resample_t(C.Structure):
 
 M1_RESAMPLE_MAX_LINE = 1024
 
+class m1_cc_row_t(C.Structure):
+    """One component's row of m1_cc_stats (include/m1hip.h); ``CC_ROW_DTYPE`` in hip/ops.py is the same layout for numpy."""
+    _fields_ = [("count", C.c_int32), ("vmax", C.c_float), ("argmax", C.c_int64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+                ("sum", C.c_int64 * 3)]
+
+
+# enum m1_cc_dtype / m1_cc_state, the labelling tile
+M1_CC_F32, M1_CC_U8 = 0, 1
+(M1_CC_ST_PEAK, M1_CC_ST_ARGMAX, M1_CC_ST_THRESHOLD, M1_CC_ST_SEL, M1_CC_ST_COUNT, M1_CC_ST_DONE, M1_CC_ST_NCAND,
+ M1_CC_ST_SPARE) = range(8)
+M1_CC_TILE = (4, 8, 32)
+
 # enum m1_label_objective / m1_feed_mode
 M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
 M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
@@ -172,6 +184,14 @@ SIGNATURES = {
     "m1_whiten": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "m1_resample_ws_bytes": (_sz, [C.POINTER(m1_resample_t), _i, _i]),
     "m1_resample": (_i, [_vp, _i, C.POINTER(m1_resample_t), _i, _i, _vp, _i, _vp, _vp]),
+    "m1_cc_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "m1_cc_label": (_i, [_vp, _i, _f, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "m1_cc_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "m1_cc_overlap": (_i, [_vp, _vp, _i, _ll, _i, _i, _vp, _vp]),
+    "m1_cc_peak": (_i, [_vp, _i, _ll, _f, _f, _i, _vp, _vp, _vp]),
+    "m1_cc_select": (_i, [_vp, _i, _ll, _vp, _vp]),
+    "m1_cc_take": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp]),
+    "m1_cc_relabel": (_i, [_vp, _vp, _i, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "m1_dropout": (_i, [_vp, _vp, _ll, _f, _vp, _u64, _i, _vp]),
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),

@@ -1222,6 +1222,155 @@ def resample(src: torch.Tensor, step, dst=None, first=(0, 0, 0), order: int = 3,
 
 
 # ---------------------------------------------------------------------------------------------------------
+# connected components, lesion candidates and matching (components.hip; detection.py is the public surface)
+# ---------------------------------------------------------------------------------------------------------
+_CC_DTYPES = {torch.float32: L.M1_CC_F32, torch.uint8: L.M1_CC_U8}
+CC_STATE_WORDS = 8
+
+
+def _cc_vol(t: torch.Tensor, what: str, dtypes) -> Tuple[int, int, int, int]:
+    _req(t)
+    if t.dim() != 4 or t.dtype not in dtypes:
+        raise RuntimeError(f"{what}: a (B,D,H,W) volume of {' / '.join(str(d) for d in dtypes)} expected, got {t.dtype} {tuple(t.shape)}")
+    return tuple(int(v) for v in t.shape)
+
+
+def _cc_same(a: torch.Tensor, b: Optional[torch.Tensor], what: str, dtype) -> None:
+    _req(b)
+    if b is not None and (b.dtype != dtype or b.shape != a.shape):
+        raise RuntimeError(f"{what}: {dtype} of shape {tuple(a.shape)} expected, got {b.dtype} {tuple(b.shape)}")
+
+
+def cc_workspace(shape, device) -> torch.Tensor:
+    """The workspace of label_components / cc_peak for (B,D,H,W) volumes (m1_cc_ws_bytes), from torch's allocator."""
+    B, D, H, W = (int(v) for v in shape)
+    return torch.empty(max(int(L.load().m1_cc_ws_bytes(B, D, H, W)), 16) // 4, dtype=torch.int32, device=device)
+
+
+def _cc_ws(ws: Optional[torch.Tensor], shape, device) -> torch.Tensor:
+    if ws is None:
+        return cc_workspace(shape, device)
+    _req(ws)
+    need = int(L.load().m1_cc_ws_bytes(*[int(v) for v in shape]))
+    if ws.numel() * ws.element_size() < need:
+        raise RuntimeError(f"components workspace: {need} bytes needed for {tuple(shape)}, got {ws.numel() * ws.element_size()}")
+    return ws
+
+
+def label_components(x: torch.Tensor, threshold=0.0, connectivity: int = 3, ws: Optional[torch.Tensor] = None):
+    """m1_cc_label: the connected components of ``x > threshold`` for a (B,D,H,W) fp32 / uint8 volume -> (labels (B,D,H,W) int32 numbered
+    as scipy.ndimage.label numbers them, per batch entry; counts (B,) int32).  ``threshold``: a number, or a (B,) fp32 device tensor
+    (one threshold per batch entry, no host read).  ``ws``: cc_workspace(x.shape), or None to allocate it."""
+    B, D, H, W = _cc_vol(x, "label_components", tuple(_CC_DTYPES))
+    thr_dev = None
+    if isinstance(threshold, torch.Tensor):
+        _req(threshold)
+        if threshold.dtype != torch.float32 or threshold.numel() != B:
+            raise RuntimeError(f"label_components: a per-sample threshold is {B} fp32 values, got {threshold.dtype} {tuple(threshold.shape)}")
+        thr_dev, threshold = threshold, 0.0
+    ws = _cc_ws(ws, x.shape, x.device)
+    labels = torch.empty(x.shape, dtype=torch.int32, device=x.device)
+    counts = torch.empty(B, dtype=torch.int32, device=x.device)
+    L.check(L.load().m1_cc_label(_p(x), _CC_DTYPES[x.dtype], float(threshold), _p(thr_dev), int(connectivity), B, D, H, W, _p(labels),
+                                 _p(counts), _p(ws), _stream()), "m1_cc_label")
+    return labels, counts
+
+
+def _cc_rows_dict(rows: torch.Tensor) -> dict:
+    """The fields of a (B,K,16) int32 tensor of m1_cc_row_t as views."""
+    r64 = rows.view(torch.int64)
+    return {"count": rows[..., 0], "max": rows.view(torch.float32)[..., 1], "argmax": r64[..., 1], "lo": rows[..., 4:7],
+            "hi": rows[..., 7:10], "sum": r64[..., 5:8], "rows": rows}
+
+
+def component_stats(labels: torch.Tensor, values: Optional[torch.Tensor] = None, max_components: int = 64) -> dict:
+    """m1_cc_stats: the per-component table of (B,D,H,W) int32 ``labels`` -> dict of (B,K,...) tensors: count, max and argmax of
+    ``values`` (linear index inside the batch entry, ties to the smallest), lo / hi (bounding box, hi exclusive), sum (int64
+    coordinate sums), and ``rows``, the raw (B,K,16) int32 table they are views of."""
+    B, D, H, W = _cc_vol(labels, "component_stats", (torch.int32,))
+    _cc_same(labels, values, "component_stats values", torch.float32)
+    K = int(max_components)
+    rows = torch.empty((B, max(K, 1), C.sizeof(L.m1_cc_row_t) // 4), dtype=torch.int32, device=labels.device)
+    L.check(L.load().m1_cc_stats(_p(labels), _p(values), B, D, H, W, K, _p(rows), _stream()), "m1_cc_stats")
+    return _cc_rows_dict(rows)
+
+
+def component_overlap(a: torch.Tensor, b: torch.Tensor, max_a: int, max_b: int) -> torch.Tensor:
+    """m1_cc_overlap: (B, max_a + 1, max_b + 1) int32 counts of the voxels with labels (a, b); row / column 0 are background."""
+    B = _cc_vol(a, "component_overlap", (torch.int32,))[0]
+    _cc_same(a, b, "component_overlap", torch.int32)
+    table = torch.empty((B, max(int(max_a), 0) + 1, max(int(max_b), 0) + 1), dtype=torch.int32, device=a.device)
+    L.check(L.load().m1_cc_overlap(_p(a), _p(b), B, a.numel() // B, int(max_a), int(max_b), _p(table), _stream()), "m1_cc_overlap")
+    return table
+
+
+def cc_state(B: int, device) -> torch.Tensor:
+    """The (8, B) int32 device state of the dynamic extraction (enum m1_cc_state); cc_peak(reset=True) initialises it."""
+    return torch.empty((CC_STATE_WORDS, int(B)), dtype=torch.int32, device=device)
+
+
+def _cc_state(state: torch.Tensor, B: int) -> None:
+    _req(state)
+    if state.dtype != torch.int32 or tuple(state.shape) != (CC_STATE_WORDS, B):
+        raise RuntimeError(f"components state: int32 {(CC_STATE_WORDS, B)} expected, got {state.dtype} {tuple(state.shape)}")
+
+
+def cc_peak(w: torch.Tensor, state: torch.Tensor, factor: float = 1.0, min_confidence: float = float("-inf"), reset: bool = False,
+            ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """m1_cc_peak: per sample of the (B,D,H,W) fp32 ``w`` the maximum and its index (ties to the smallest) into ``state``, with
+    THRESHOLD = PEAK / factor and DONE set where not PEAK > min_confidence."""
+    B = _cc_vol(w, "cc_peak", (torch.float32,))[0]
+    _cc_state(state, B)
+    ws = _cc_ws(ws, w.shape, w.device)
+    L.check(L.load().m1_cc_peak(_p(w), B, w.numel() // B, float(factor), float(min_confidence), int(bool(reset)), _p(state), _p(ws),
+                                _stream()), "m1_cc_peak")
+    return state
+
+
+def cc_select(labels: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+    """m1_cc_select: SEL = the label at each sample's ARGMAX and COUNT = its voxels."""
+    B = _cc_vol(labels, "cc_select", (torch.int32,))[0]
+    _cc_state(state, B)
+    L.check(L.load().m1_cc_select(_p(labels), B, labels.numel() // B, _p(state), _stream()), "m1_cc_select")
+    return state
+
+
+def cc_take(labels: torch.Tensor, state: torch.Tensor, w: torch.Tensor, detection_map: torch.Tensor, candidates: torch.Tensor,
+            confidences: torch.Tensor, min_voxels: int, reset: bool = False, w_src: Optional[torch.Tensor] = None) -> None:
+    """m1_cc_take: the selected component leaves ``w`` and, when it has ``min_voxels``, becomes the next candidate of its sample in
+    ``detection_map`` / ``candidates`` / ``confidences`` (B, n_max); ``reset`` initialises those three, and ``w`` from ``w_src`` when given (the round then ran on ``w_src``)."""
+    B = _cc_vol(labels, "cc_take", (torch.int32,))[0]
+    _cc_state(state, B)
+    _cc_same(labels, w, "cc_take w", torch.float32)
+    _cc_same(labels, w_src, "cc_take w_src", torch.float32)
+    _cc_same(labels, detection_map, "cc_take detection_map", torch.float32)
+    _cc_same(labels, candidates, "cc_take candidates", torch.int32)
+    _req(confidences)
+    if confidences.dtype != torch.float32 or confidences.dim() != 2 or confidences.shape[0] != B:
+        raise RuntimeError(f"cc_take: confidences are fp32 (B, n), got {confidences.dtype} {tuple(confidences.shape)}")
+    L.check(L.load().m1_cc_take(_p(labels), _p(state), _p(w_src if reset else None), _p(w), _p(detection_map), _p(candidates), _p(confidences), B, labels.numel() // B,
+                                int(confidences.shape[1]), int(min_voxels), int(bool(reset)), _stream()), "m1_cc_take")
+
+
+def cc_relabel(labels: torch.Tensor, stats: dict, min_voxels: int):
+    """m1_cc_relabel: the components of ``labels`` with at least ``min_voxels`` voxels, renumbered in order, from the table of
+    component_stats -> (detection_map fp32, candidates int32, confidences (B,K) fp32, ncand (B,) int32)."""
+    B = _cc_vol(labels, "cc_relabel", (torch.int32,))[0]
+    rows = stats["rows"]
+    _req(rows)
+    K = int(rows.shape[1])
+    dev = labels.device
+    cmap = torch.empty((B, K), dtype=torch.int32, device=dev)
+    det = torch.empty(labels.shape, dtype=torch.float32, device=dev)
+    cand = torch.empty(labels.shape, dtype=torch.int32, device=dev)
+    conf = torch.empty((B, K), dtype=torch.float32, device=dev)
+    ncand = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(L.load().m1_cc_relabel(_p(labels), _p(rows), B, labels.numel() // B, K, int(min_voxels), _p(cmap), _p(det), _p(cand), _p(conf),
+                                   _p(ncand), _stream()), "m1_cc_relabel")
+    return det, cand, conf, ncand
+
+
+# ---------------------------------------------------------------------------------------------------------
 # dropout (standalone), cast
 # ---------------------------------------------------------------------------------------------------------
 class _Dropout(torch.autograd.Function):
