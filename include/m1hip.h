@@ -584,6 +584,57 @@ int m1_cc_take(const int* labels, int* state, const float* w_src, float* w, floa
 int m1_cc_relabel(const int* labels, const m1_cc_row_t* rows, int B, long long n, int max_components, int min_voxels, int* map,
                   float* detection_map, int* candidates, float* confidences, int* ncand, void* stream);
 
+/* ---- surface-distance metrics of label maps with voxel spacing : train_model.py's `AnatomySegmentationValidation` import
+ *      (csrc/surface.hip; surface_distance.py is the public surface.  The reference never shipped the callback: the definitions are
+ *      pinned against scipy.ndimage binary_erosion / distance_transform_edt and numpy's linear percentile) ----
+ * Label maps are (B, D, H, W) uint8 or int32, n = D * H * W.  For class k of batch entry b (slice s = b * K + k): A = (pred == labels[k]),
+ * B = (truth == labels[k]); border(M) = the voxels of M with at least one of their six face neighbours outside M, outside the volume
+ * counting as background.  Common rules: NULL or misaligned pointers, B or an extent <= 0, K outside 1..M1_SD_MAX_CLASSES, a spacing
+ * that is not finite and positive, T outside 0..M1_SD_MAX_TOLERANCES, a NaN tolerance, a percentile outside [0, 100]: M1_ERR_BAD_ARG;
+ * an axis longer than M1_SD_MAX_LINE (m1_sd_distance only), a dtype outside the enum, n >= 2^31 - 1, more than 65535 stacked volumes:
+ * M1_ERR_UNSUPPORTED; both before any launch.  No atomics on global memory, no memset / memcpy nodes, no host synchronisation, no
+ * kernel waits for another workgroup; sums are folded in a fixed order: results are bit-identical run to run.
+ * m1_sd_border: borders (2, B, K, D, H, W) uint8 = border(A) then border(B) as 0 / 1; counts (B, K, 5) int64 = {|border(A)|, |border(B)|,
+ *   |A|, |B|, |A and B|}.  `labels`: K ints in HOST memory.  ws: m1_sd_ws_bytes(M1_SD_STAGE_BORDER, ...) bytes, 4-byte aligned.  2 launches.
+ * m1_sd_distance: dist (N, D, H, W) fp32 = the distance of every voxel to the nearest non-zero voxel of its own volume of `mask`
+ *   (N, D, H, W) uint8: the exact minimum of sqrt(sum_i (spacing[i] * delta_i)^2), spacing = 3 doubles in HOST memory in array-axis order
+ *   (D, H, W), formed in fp64 and rounded once to fp32; +inf where the volume has no non-zero voxel.  Three separable passes, along W, H,
+ *   D.  ws: m1_sd_ws_bytes(M1_SD_STAGE_DISTANCE, N, 1, D, H, W) bytes, 16-byte aligned.  3 launches.
+ * m1_sd_metrics: borders as m1_sd_border writes them, dist (2, B, K, D, H, W) fp32 = m1_sd_distance of those 2 * B * K volumes (not NaN,
+ *   not negative).  Direction 0 is the set d_AB = {dist[1][s][x] : borders[0][s][x] != 0}, direction 1 the set d_BA with the roles
+ *   swapped.  rows (B, K) of m1_sd_row_t: n / sum / le[t] = size, fp64 sum and number of elements <= tolerances[t] of each directed set;
+ *   hd_ab / hd_ba = the directed maxima, hd their maximum; mean_ab / mean_ba = sum / n, assd = (mean_ab + mean_ba) / 2; hdq_ab / hdq_ba /
+ *   hdq = the `percentile`-th percentile of d_AB, of d_BA and of the pooled multiset, by numpy's linear rule: h = (n - 1) * percentile /
+ *   100, lo = floor(h), a[lo] + (h - lo) * (a[min(lo + 1, n - 1)] - a[lo]) in fp64, rounded once to fp32; nsd[t] = (le_ab[t] + le_ba[t])
+ *   / (n_ab + n_ba).  A set that is empty makes every distance result of the row NaN; nsd is then NaN too, except that two empty sets
+ *   give 1; nsd[t] for t >= T is NaN.  dice = 2 |A and B| / (|A| + |B|) from `counts` (the table of m1_sd_border; NaN when both are
+ *   empty or counts is NULL).  `tolerances`: T floats in HOST memory.  ws: m1_sd_ws_bytes(M1_SD_STAGE_METRICS, ...) bytes, 16-byte
+ *   aligned.  11 launches: partial statistics and their fold, four rounds of histogram and scan of an 8-bit radix select on the fp32
+ *   bit pattern, the rows. */
+#define M1_SD_MAX_CLASSES 8
+#define M1_SD_MAX_TOLERANCES 4
+#define M1_SD_MAX_LINE 256
+enum m1_sd_dtype { M1_SD_U8 = 0, M1_SD_I32 = 1 };
+enum m1_sd_stage { M1_SD_STAGE_BORDER = 0, M1_SD_STAGE_DISTANCE = 1, M1_SD_STAGE_METRICS = 2 };
+typedef struct {
+    int64_t n[2];
+    int64_t le[2][4];
+    double sum[2];
+    float hd, hd_ab, hd_ba;
+    float assd, mean_ab, mean_ba;
+    float hdq, hdq_ab, hdq_ba;
+    float dice;
+    float nsd[4];
+    float _pad[2];
+} m1_sd_row_t; /* 160 bytes */
+/* pure host.  0 for arguments the stage's entry point would reject.  M1_SD_STAGE_DISTANCE: B = the number of stacked volumes, K unused. */
+size_t m1_sd_ws_bytes(int stage, int B, int K, int D, int H, int W);
+int m1_sd_border(const void* pred, const void* truth, int dtype, const int* labels, int K, int B, int D, int H, int W, uint8_t* borders,
+                 long long* counts, void* ws, void* stream);
+int m1_sd_distance(const uint8_t* mask, int N, int D, int H, int W, const double* spacing, float* dist, void* ws, void* stream);
+int m1_sd_metrics(const uint8_t* borders, const float* dist, const long long* counts, int B, int K, int D, int H, int W, double percentile,
+                  const float* tolerances, int T, m1_sd_row_t* rows, void* ws, void* stream);
+
 /* ---- MonteCarloDropout / Dropout : B:142-143 ; N:462-463 (Philox4x32-10, mask regenerated in bwd) ---- */
 int m1_dropout(const void* x, void* y, long long n, float rate, const uint64_t* rng, uint64_t layer_id, int dtype,
                void* stream);

@@ -1,5 +1,5 @@
 """Reference-shaped import path: ``import model.unets as unets; import model.losses as losses`` (as in the
-reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators``, ``model.preprocess`` and ``model.detection`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
+reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators``, ``model.preprocess``, ``model.detection`` and ``model.surface_distance`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
 import importlib
 import os
 import sys
@@ -16,6 +16,7 @@ augmentations = _pkg.augmentations
 data_generators = _pkg.data_generators
 preprocess = _pkg.preprocess
 detection = _pkg.detection
+surface_distance = _pkg.surface_distance
 sys.modules[__name__ + ".unets"] = unets
 sys.modules[__name__ + ".unets.networks"] = unets.networks
 sys.modules[__name__ + ".unets.network_blocks"] = unets.network_blocks
@@ -25,3 +26,4 @@ sys.modules[__name__ + ".augmentations"] = augmentations
 sys.modules[__name__ + ".data_generators"] = data_generators
 sys.modules[__name__ + ".preprocess"] = preprocess
 sys.modules[__name__ + ".detection"] = detection
+sys.modules[__name__ + ".surface_distance"] = surface_distance

@@ -19,5 +19,7 @@ from . import augmentations  # noqa: F401
 from . import data_generators  # noqa: F401
 from . import preprocess     # noqa: F401
 from . import detection      # noqa: F401
+from . import surface_distance  # noqa: F401
 
-__all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp", "augmentations", "data_generators", "preprocess", "detection"]
+__all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp", "augmentations", "data_generators", "preprocess", "detection",
+           "surface_distance"]

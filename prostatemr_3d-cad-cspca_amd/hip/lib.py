@@ -95,6 +95,18 @@ M1_CC_F32, M1_CC_U8 = 0, 1
  M1_CC_ST_SPARE) = range(8)
 M1_CC_TILE = (4, 8, 32)
 
+class m1_sd_row_t(C.Structure):
+    """One (batch entry, class) row of m1_sd_metrics (include/m1hip.h); hip/ops.py views the same 160 bytes as 40 int32 words."""
+    _fields_ = [("n", C.c_int64 * 2), ("le", (C.c_int64 * 4) * 2), ("sum", C.c_double * 2), ("hd", C.c_float), ("hd_ab", C.c_float),
+                ("hd_ba", C.c_float), ("assd", C.c_float), ("mean_ab", C.c_float), ("mean_ba", C.c_float), ("hdq", C.c_float),
+                ("hdq_ab", C.c_float), ("hdq_ba", C.c_float), ("dice", C.c_float), ("nsd", C.c_float * 4), ("_pad", C.c_float * 2)]
+
+
+# enum m1_sd_dtype / m1_sd_stage, the limits of the surface-distance entry points
+M1_SD_U8, M1_SD_I32 = 0, 1
+M1_SD_STAGE_BORDER, M1_SD_STAGE_DISTANCE, M1_SD_STAGE_METRICS = 0, 1, 2
+M1_SD_MAX_CLASSES, M1_SD_MAX_TOLERANCES, M1_SD_MAX_LINE = 8, 4, 256
+
 # enum m1_label_objective / m1_feed_mode
 M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
 M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
@@ -192,6 +204,10 @@ SIGNATURES = {
     "m1_cc_select": (_i, [_vp, _i, _ll, _vp, _vp]),
     "m1_cc_take": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp]),
     "m1_cc_relabel": (_i, [_vp, _vp, _i, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m1_sd_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "m1_sd_border": (_i, [_vp, _vp, _i, C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "m1_sd_distance": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_d), _vp, _vp, _vp]),
+    "m1_sd_metrics": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, C.POINTER(_f), _i, _vp, _vp, _vp]),
     "m1_dropout": (_i, [_vp, _vp, _ll, _f, _vp, _u64, _i, _vp]),
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),

@@ -1371,6 +1371,103 @@ def cc_relabel(labels: torch.Tensor, stats: dict, min_voxels: int):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# surface-distance metrics (surface.hip; surface_distance.py is the public surface)
+# ---------------------------------------------------------------------------------------------------------
+_SD_DTYPES = {torch.uint8: L.M1_SD_U8, torch.int32: L.M1_SD_I32}
+SD_ROW_WORDS = C.sizeof(L.m1_sd_row_t) // 4
+SD_COUNT_KEYS = ("n_pred", "n_truth", "vol_pred", "vol_truth", "vol_both")
+
+
+def sd_workspace(stage: int, B: int, K: int, shape, device) -> torch.Tensor:
+    """The workspace of one surface-distance stage (L.M1_SD_STAGE_*) for (D,H,W) volumes (m1_sd_ws_bytes), from torch's allocator.
+    For the distance stage ``B`` is the number of stacked volumes and ``K`` is not used."""
+    D, H, W = (int(v) for v in shape)
+    return torch.empty(max(int(L.load().m1_sd_ws_bytes(int(stage), int(B), int(K), D, H, W)), 16) // 4, dtype=torch.int32, device=device)
+
+
+def _sd_ws(ws: Optional[torch.Tensor], stage: int, B: int, K: int, shape, device) -> torch.Tensor:
+    if ws is None:
+        return sd_workspace(stage, B, K, shape, device)
+    _req(ws)
+    need = int(L.load().m1_sd_ws_bytes(int(stage), int(B), int(K), *[int(v) for v in shape]))
+    if ws.numel() * ws.element_size() < need:
+        raise RuntimeError(f"surface-distance workspace: {need} bytes needed for {tuple(shape)}, got {ws.numel() * ws.element_size()}")
+    return ws
+
+
+def _sd_labels(labels) -> Tuple[int, ...]:
+    labels = tuple(int(v) for v in labels)
+    if not 1 <= len(labels) <= L.M1_SD_MAX_CLASSES:
+        raise RuntimeError(f"surface distance: 1..{L.M1_SD_MAX_CLASSES} class ids expected, got {len(labels)}")
+    return labels
+
+
+def sd_border(pred: torch.Tensor, truth: torch.Tensor, labels=(1,), ws: Optional[torch.Tensor] = None):
+    """m1_sd_border: for (B,D,H,W) uint8 / int32 label maps and K class ids -> (borders (2,B,K,D,H,W) uint8: the 6-neighbourhood
+    border voxels of ``pred == labels[k]`` then of ``truth == labels[k]``, outside the volume counting as background; counts (B,K,5)
+    int64: SD_COUNT_KEYS)."""
+    B, D, H, W = _cc_vol(pred, "sd_border", tuple(_SD_DTYPES))
+    _cc_same(pred, truth, "sd_border truth", pred.dtype)
+    labels = _sd_labels(labels)
+    K = len(labels)
+    ws = _sd_ws(ws, L.M1_SD_STAGE_BORDER, B, K, (D, H, W), pred.device)
+    borders = torch.empty((2, B, K, D, H, W), dtype=torch.uint8, device=pred.device)
+    counts = torch.empty((B, K, 5), dtype=torch.int64, device=pred.device)
+    L.check(L.load().m1_sd_border(_p(pred), _p(truth), _SD_DTYPES[pred.dtype], (C.c_int * K)(*labels), K, B, D, H, W, _p(borders),
+                                  _p(counts), _p(ws), _stream()), "m1_sd_border")
+    return borders, counts
+
+
+def sd_distance(mask: torch.Tensor, spacing=(1.0, 1.0, 1.0), ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """m1_sd_distance: the exact Euclidean distance of every voxel of an (N,D,H,W) uint8 stack to the nearest non-zero voxel of its own
+    volume, ``spacing`` in array-axis order (D,H,W); fp64 inside, fp32 out; +inf in a volume without a non-zero voxel."""
+    N, D, H, W = _cc_vol(mask, "sd_distance", (torch.uint8,))
+    spacing = tuple(float(v) for v in spacing)
+    if len(spacing) != 3:
+        raise RuntimeError(f"sd_distance: three spacings (D,H,W) expected, got {spacing}")
+    ws = _sd_ws(ws, L.M1_SD_STAGE_DISTANCE, N, 1, (D, H, W), mask.device)      # (an unsupported shape asks for nothing and is refused below)
+    dist = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
+    L.check(L.load().m1_sd_distance(_p(mask), N, D, H, W, (C.c_double * 3)(*spacing), _p(dist), _p(ws), _stream()), "m1_sd_distance")
+    return dist
+
+
+def _sd_rows_dict(rows: torch.Tensor, T: int) -> dict:
+    """The fields of a (B,K,40) int32 tensor of m1_sd_row_t as views."""
+    r64, rf, rd = rows.view(torch.int64), rows.view(torch.float32), rows.view(torch.float64)
+    out = {"n_ab": r64[..., 0], "n_ba": r64[..., 1], "le_ab": r64[..., 2:2 + T], "le_ba": r64[..., 6:6 + T], "sum_ab": rd[..., 10],
+           "sum_ba": rd[..., 11], "rows": rows}
+    for j, key in enumerate(("hd", "hd_ab", "hd_ba", "assd", "mean_ab", "mean_ba", "hdq", "hdq_ab", "hdq_ba", "dice")):
+        out[key] = rf[..., 24 + j]
+    out["nsd"] = rf[..., 34:34 + T]
+    return out
+
+
+def sd_metrics(borders: torch.Tensor, dist: torch.Tensor, counts: Optional[torch.Tensor] = None, percentile: float = 95.0,
+               tolerances=(), ws: Optional[torch.Tensor] = None) -> dict:
+    """m1_sd_metrics: from the (2,B,K,D,H,W) border masks of sd_border and the distances of those volumes to their own borders
+    (sd_distance of the 2*B*K stack) -> dict of (B,K) device tensors (views of ``rows``, the raw (B,K,40) int32 table): the directed
+    counts, fp64 sums and maxima, hd, assd, the ``percentile``-th percentiles hdq_ab / hdq_ba / hdq (pooled), nsd (B,K,T) and, when
+    the ``counts`` of sd_border are given, dice."""
+    _req(borders, dist, counts)
+    if borders.dim() != 6 or borders.shape[0] != 2 or borders.dtype != torch.uint8:
+        raise RuntimeError(f"sd_metrics: (2,B,K,D,H,W) uint8 border masks expected, got {borders.dtype} {tuple(borders.shape)}")
+    if dist.shape != borders.shape or dist.dtype != torch.float32:
+        raise RuntimeError(f"sd_metrics: fp32 distances of shape {tuple(borders.shape)} expected, got {dist.dtype} {tuple(dist.shape)}")
+    _, B, K, D, H, W = (int(v) for v in borders.shape)
+    if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (B, K, 5)):
+        raise RuntimeError(f"sd_metrics: counts are int64 {(B, K, 5)}, got {counts.dtype} {tuple(counts.shape)}")
+    tolerances = tuple(float(v) for v in tolerances)
+    T = len(tolerances)
+    if T > L.M1_SD_MAX_TOLERANCES:
+        raise RuntimeError(f"sd_metrics: at most {L.M1_SD_MAX_TOLERANCES} tolerances per call, got {T}")
+    ws = _sd_ws(ws, L.M1_SD_STAGE_METRICS, B, K, (D, H, W), borders.device)
+    rows = torch.empty((B, K, SD_ROW_WORDS), dtype=torch.int32, device=borders.device)
+    L.check(L.load().m1_sd_metrics(_p(borders), _p(dist), _p(counts), B, K, D, H, W, float(percentile), (C.c_float * max(T, 1))(*tolerances),
+                                   T, _p(rows), _p(ws), _stream()), "m1_sd_metrics")
+    return _sd_rows_dict(rows, T)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # dropout (standalone), cast
 # ---------------------------------------------------------------------------------------------------------
 class _Dropout(torch.autograd.Function):
