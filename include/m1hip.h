@@ -463,7 +463,7 @@ int m1_label_prepare(const uint8_t* ann, const float* image, float* x_out, float
  * a mode or dtype outside the enums: M1_ERR_UNSUPPORTED; both before any launch.  ws: m1_preprocess_ws_bytes bytes, 8-byte aligned
  * (one buffer serves m1_order_stats and then m1_whiten of one batch); its contents need no initialisation.  No atomics on global
  * memory, no memset / memcpy nodes, no host synchronisation; results are bit-identical run to run. */
-enum m1_raw_dtype { M1_RAW_F32 = 0, M1_RAW_I16 = 1 };
+enum m1_raw_dtype { M1_RAW_F32 = 0, M1_RAW_I16 = 1, M1_RAW_I32 = 2 };       /* (M1_RAW_I32: m1_restore with order 0 only) */
 enum m1_pad_mode { M1_PAD_CONSTANT = 0, M1_PAD_EDGE = 1, M1_PAD_REFLECT = 2, M1_PAD_SYMMETRIC = 3 };
 typedef struct { int src[3]; int dst[3]; int start[3]; int mode; float cval; } m1_crop_pad_t;
 /* pure host; nq = 0 sizes the buffer for m1_whiten alone.  0 for arguments the entry points would reject. */
@@ -517,6 +517,35 @@ typedef struct { int src[3]; int dst[3]; int first[3]; int order; double step[3]
 /* pure host.  0 for arguments m1_resample would reject, and for order 0. */
 size_t m1_resample_ws_bytes(const m1_resample_t* g, int B, int C);
 int m1_resample(const void* src, int src_dtype, const m1_resample_t* g, int B, int C, void* out, int out_dtype, void* ws, void* stream);
+
+/* ---- back-projection onto the scan's own grid (csrc/restore.hip; preprocess.restore is the public surface) ----
+ * The inverse of the geometry of preprocess.prepare_scan (resampling to the network's spacing, then crop / pad to the network's
+ * size): a map (B, src[0], src[1], src[2], C) on the network's grid is put back on the scan's grid (B, dst[0], dst[1], dst[2]).  The
+ * reference ships no such step; it fixes the forward geometry (P:52-71, P:74-98), of which this is the exact inverse.
+ * m1_restore_t per axis: dst = the scan's length, ratio = spacing / out_spacing (the reciprocal of m1_resample_t's step), (first,
+ * count) = the part of the resampled grid the crop kept, lo = the pad voxels in front on the network grid: the real voxels of the
+ * network axis are [lo, lo + count).  Scan voxel i sits at the window coordinate u = i * ratio - first (fp64, product then
+ * difference) and is inside when -0.5 <= u < count - 0.5 on every axis; outside voxels receive defval (deflabel in the label
+ * output) and read nothing.
+ *   order 1: taps floor(u) and floor(u) + 1, each clamped to [0, count - 1] and then offset by lo, weight y = fp32(u - floor(u)), one
+ *            axis is a * (1 - y) + b * y in fp32, axes applied in the order 0, 1, 2.  src fp32 -> prob fp32.
+ *   order 0: the voxel at floor(u + 0.5), clamped the same way.  src fp32 / int16 / int32 (M1_RAW_I32) -> prob of the same type (defval,
+ *            a float, is converted to it: exact up to 2^24 in magnitude).
+ * A pad voxel of the network grid is never read.  Outputs, either or both, from one pass over the taps: prob (B, dst..., nsel) = the
+ * channels [c0, c0 + nsel) of the restored map (c0 and nsel are not read when prob is NULL); label (B, dst...) uint8 = the argmax
+ * over ALL C restored channels, taken on the values that would be stored (strict >, channels in rising order: the first maximum
+ * wins).  One launch, no workspace.  A lane stores runs of 4 consecutive voxels: 16-byte stores (8 for int16; 4 for the labels) where
+ * the run is whole and starts at a multiple of 4 elements of an aligned pointer, element stores otherwise, and always for nsel >
+ * M1_RESTORE_MAX_SEL (the widest selection a lane keeps in registers).
+ * NULL src or g, both outputs NULL, B or C < 1, a channel range outside [0, C), C > 255 or a deflabel outside [0, 255] with a label
+ * output, an extent or count < 1, first or lo < 0, lo + count > src, a ratio that is not finite and positive, an order other than
+ * 0 / 1, an integer type with order 1, a pointer not aligned to its element: M1_ERR_BAD_ARG.  A dtype outside the enum, a source
+ * (times B * C) or an output (times B) of 2^31 voxels or more: M1_ERR_UNSUPPORTED.  Both before any
+ * launch.  No atomics, no memset / memcpy nodes, no host synchronisation; results are bit-identical run to run. */
+#define M1_RESTORE_MAX_SEL 4
+typedef struct { int src[3]; int dst[3]; int first[3]; int count[3]; int lo[3]; int order; double ratio[3]; float defval; int deflabel; } m1_restore_t;
+int m1_restore(const void* src, int src_dtype, const m1_restore_t* g, int B, int C, int c0, int nsel, void* prob, void* label,
+               void* stream);
 
 /* ---- connected components, lesion candidates and matching : train_model.py's `regionprops` import, callbacks.py's `compute_FROC`
  *      (csrc/components.hip; detection.py is the public surface.  The reference ships neither function: the numbering is pinned

@@ -71,7 +71,7 @@ class m1_crop_pad_t(C.Structure):
 
 
 # enum m1_raw_dtype / m1_pad_mode
-M1_RAW_F32, M1_RAW_I16 = 0, 1
+M1_RAW_F32, M1_RAW_I16, M1_RAW_I32 = 0, 1, 2          # (M1_RAW_I32: m1_restore with order 0 only)
 M1_PAD_CONSTANT, M1_PAD_EDGE, M1_PAD_REFLECT, M1_PAD_SYMMETRIC = 0, 1, 2, 3
 
 
@@ -82,6 +82,16 @@ class m1_resample_t(C.Structure):
 
 
 M1_RESAMPLE_MAX_LINE = 1024
+
+
+class m1_restore_t(C.Structure):
+    """The back-projection geometry of m1_restore (include/m1hip.h): per axis the scan's length ``dst``, ratio = spacing / out_spacing,
+    the kept window (first, count) of the resampled grid and the pad voxels ``lo`` in front on the network grid."""
+    _fields_ = [("src", C.c_int * 3), ("dst", C.c_int * 3), ("first", C.c_int * 3), ("count", C.c_int * 3), ("lo", C.c_int * 3),
+                ("order", C.c_int), ("ratio", C.c_double * 3), ("defval", C.c_float), ("deflabel", C.c_int)]
+
+
+M1_RESTORE_MAX_SEL = 4              # the widest channel selection m1_restore stores with vector stores (wider: element stores)
 
 class m1_cc_row_t(C.Structure):
     """One component's row of m1_cc_stats (include/m1hip.h); ``CC_ROW_DTYPE`` in hip/ops.py is the same layout for numpy."""
@@ -196,6 +206,7 @@ SIGNATURES = {
     "m1_whiten": (_i, [_vp, _i, C.POINTER(m1_crop_pad_t), _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "m1_resample_ws_bytes": (_sz, [C.POINTER(m1_resample_t), _i, _i]),
     "m1_resample": (_i, [_vp, _i, C.POINTER(m1_resample_t), _i, _i, _vp, _i, _vp, _vp]),
+    "m1_restore": (_i, [_vp, _i, C.POINTER(m1_restore_t), _i, _i, _i, _i, _vp, _vp, _vp]),
     "m1_cc_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "m1_cc_label": (_i, [_vp, _i, _f, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "m1_cc_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

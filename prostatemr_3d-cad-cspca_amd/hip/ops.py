@@ -1221,6 +1221,47 @@ def resample(src: torch.Tensor, step, dst=None, first=(0, 0, 0), order: int = 3,
     return out
 
 
+_RESTORE_DTYPES = {**_RAW_DTYPES, torch.int32: L.M1_RAW_I32}
+
+
+def restore_geom(src_dims, dst, ratio, first, count, lo, order: int = 1, default_value: float = 0.0,
+                 default_label: int = 0) -> L.m1_restore_t:
+    """The m1_restore_t of a (D,H,W) map on the network's grid: scan voxel i of an axis of ``dst`` voxels sits at the window coordinate
+    i * ratio - first and reads the real voxels [lo, lo + count) of the network axis (preprocess.restore_geometry computes the five)."""
+    if any(len(v) != 3 for v in (src_dims, dst, ratio, first, count, lo)):
+        raise RuntimeError(f"back-projection geometry: three values per field expected, got {tuple(src_dims)}, {tuple(dst)}, {tuple(ratio)}, "
+                           f"{tuple(first)}, {tuple(count)}, {tuple(lo)}")
+    if order not in (0, 1):
+        raise NotImplementedError(f"restore: order {order!r} is not built; 0 (nearest) and 1 (linear) are")
+    g = L.m1_restore_t()
+    g.src[:], g.dst[:] = [int(v) for v in src_dims], [int(v) for v in dst]
+    g.first[:], g.count[:], g.lo[:] = [int(v) for v in first], [int(v) for v in count], [int(v) for v in lo]
+    g.ratio[:] = [float(v) for v in ratio]
+    g.order, g.defval, g.deflabel = int(order), float(default_value), int(default_label)
+    return g
+
+
+def restore(src: torch.Tensor, geom: L.m1_restore_t, c0: int = 0, nsel: Optional[int] = None, prob: bool = True, label: bool = False):
+    """m1_restore: a (B,D,H,W,C) fp32 map on the network's grid (int16 / int32 as well for order 0) -> on the scan's grid ``geom.dst``, in one
+    launch: ``prob`` (B,*dst,nsel) = the channels [c0, c0 + nsel) in the source's dtype (nsel None: all from c0 on) and / or ``label``
+    (B,*dst) uint8 = the argmax over all C restored channels.  Returns the one asked for, or (prob, label)."""
+    _req(src)
+    if src.dim() != 5 or src.dtype not in _RESTORE_DTYPES:
+        raise RuntimeError(f"restore: an fp32 / int16 / int32 map (B,D,H,W,C) expected, got {src.dtype} {tuple(src.shape)}")
+    B, Cn, raw = int(src.shape[0]), int(src.shape[4]), _RESTORE_DTYPES[src.dtype]
+    if tuple(geom.src) != tuple(int(v) for v in src.shape[1:4]):
+        raise RuntimeError(f"restore: the geometry is for a source {tuple(geom.src)}, got {tuple(src.shape[1:4])}")
+    if not (prob or label):
+        raise RuntimeError("restore: at least one of prob / label expected")
+    c0 = int(c0)
+    nsel = Cn - c0 if nsel is None else int(nsel)
+    dst = [int(v) for v in geom.dst]
+    out = torch.empty((B, *dst, nsel), dtype=src.dtype, device=src.device) if prob else None
+    lab = torch.empty((B, *dst), dtype=torch.uint8, device=src.device) if label else None
+    L.check(L.load().m1_restore(_p(src), raw, C.byref(geom), B, Cn, c0, nsel, _p(out), _p(lab), _stream()), "m1_restore")
+    return (out, lab) if prob and label else out if prob else lab
+
+
 # ---------------------------------------------------------------------------------------------------------
 # connected components, lesion candidates and matching (components.hip; detection.py is the public surface)
 # ---------------------------------------------------------------------------------------------------------

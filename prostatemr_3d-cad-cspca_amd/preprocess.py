@@ -30,6 +30,12 @@ installed where this is built.  One known difference: ITK truncates the causal s
 scipy) sums it exactly, the kernels truncate it at 24 terms (2.6e-14): at most 1e-10 relative.  ``prepare_scan`` chains the resampler
 and ``prepare_input`` on the device and resamples only the part of the grid the crop keeps.
 
+``restore`` is the way back: a map on the network's grid (a softmax, an entropy, a candidate or label map) put on the scan's own grid, the
+exact inverse of prepare_scan's geometry (``restore_geometry``, from the same ``scan_window`` / ``crop_or_pad_starts`` / spacings):
+linear interpolation for probabilities, nearest neighbour for label-like maps, voxels the network never saw get a default, and a pad
+voxel of the network grid is never read.  The reference ships no such step (it has no inference script); ``restore_host`` is the
+restatement the kernel of csrc/restore.hip is measured against, pinned against scipy.ndimage.map_coordinates(order=1, mode='nearest').
+
 Differences from the reference's resample_img, on purpose: the default pixel value is a parameter that defaults to 0 (P:66 passes
 GetPixelIDValue(), the pixel-TYPE enum, by accident); image results are fp32 (ITK casts back to the input pixel type); direction and
 origin do not enter, because P:63-64 keep both.
@@ -40,6 +46,7 @@ input is outside the contract (P:38's ``image * 0.`` keeps NaNs by accident).
 """
 from __future__ import annotations
 
+import collections
 import math
 from typing import Sequence, Tuple
 
@@ -426,3 +433,170 @@ def prepare_scan(raw: torch.Tensor, spacing, out_spacing, img_size, percentile=N
     window = scan_window(raw.shape[1:4], spacing, out_spacing, img_size)
     vol = _resample_device(raw.contiguous(), spacing, out_spacing, False, default_value, window)
     return prepare_input(vol, img_size, percentile=percentile, pad_mode=pad_mode, constant_values=constant_values, dtype=dtype)
+
+
+# ---- back onto the scan's own grid ---------------------------------------------------------------------------------------------
+RestoreAxis = collections.namedtuple("RestoreAxis", "n ratio first count lo size")     # one axis of restore_geometry
+
+
+def restore_geometry(scan_shape, spacing, out_spacing, img_size):
+    """What prepare_scan did to a scan of ``scan_shape`` at ``spacing``, per axis, as a RestoreAxis: n = the scan's length; ratio =
+    spacing / out_spacing in fp64 (the reciprocal of resample_steps' step); (first, count) = scan_window's part of the resampled grid
+    that the crop kept; lo = the pad voxels in front on the network grid, so that its real voxels are [lo, lo + count); size = the
+    network's length.  Scan voxel i sits at the window coordinate u = i * ratio - first."""
+    if not (len(scan_shape) == len(img_size) == 3) or any(int(v) < 1 for v in tuple(scan_shape) + tuple(img_size)):
+        raise ValueError(f"restore: three positive scan extents and three positive network extents expected, got {tuple(scan_shape)}, "
+                         f"{tuple(img_size)}")
+    resample_steps(spacing, out_spacing)                   # (ValueError unless both are three positive spacings)
+    window = scan_window(scan_shape, spacing, out_spacing, img_size)
+    axes = []
+    for a in range(3):
+        first, count = window[a]
+        lo = -crop_or_pad_starts((count,), (img_size[a],))[0]
+        assert lo >= 0 and lo + count <= int(img_size[a])
+        axes.append(RestoreAxis(int(scan_shape[a]), float(spacing[a]) / float(out_spacing[a]), first, count, lo, int(img_size[a])))
+    return tuple(axes)
+
+
+def restore_coords(axis: RestoreAxis):
+    """(u, inside) of the scan voxels of an axis: u = i * ratio - first in fp64, inside = -0.5 <= u < count - 0.5 (resample_coords'
+    rule on the kept window)."""
+    u = np.arange(axis.n, dtype=np.float64) * np.float64(axis.ratio) - np.float64(axis.first)
+    return u, (u >= -0.5) & (u < axis.count - 0.5)
+
+
+def restore_inside(geom) -> np.ndarray:
+    """The (d,h,w) mask of the scan voxels that lie inside on every axis."""
+    inside = np.ones((), dtype=bool)
+    for a, ax in enumerate(geom):
+        shape = [1, 1, 1]
+        shape[a] = ax.n
+        inside = inside & restore_coords(ax)[1].reshape(shape)
+    return inside
+
+
+def restore_host(pred: np.ndarray, scan_shape, spacing, out_spacing, order=1, default_value=0, dtype=np.float64) -> np.ndarray:
+    """The restatement the kernel of csrc/restore.hip is measured against, on a (D,H,W[,C]) array whose spatial shape is the network's
+    size.  Order 1: the input is rounded to fp32 first; per axis, in the order 0, 1, 2, the taps floor(u) and floor(u) + 1, each
+    clamped to [0, count - 1] and then offset by lo, weight y = dtype(u - floor(u)) (coordinate, floor and fraction in fp64), and
+    a * (1 - y) + b * y in ``dtype`` values.  Order 0: a gather at floor(u + 0.5), clamped the same way, dtype kept.  Voxels outside on
+    any axis are ``default_value``; a pad voxel of the network grid is never read."""
+    pred = np.asarray(pred)
+    if pred.ndim not in (3, 4):
+        raise ValueError(f"restore: a (D,H,W[,C]) array expected, got shape {tuple(pred.shape)}")
+    if order not in (0, 1):
+        raise NotImplementedError(f"restore: order {order!r} is not built; 0 (nearest) and 1 (linear) are")
+    geom = restore_geometry(scan_shape, spacing, out_spacing, pred.shape[:3])
+    inside = restore_inside(geom)
+    if pred.ndim == 4:
+        inside = inside[..., None]
+    coords = [restore_coords(ax) for ax in geom]
+    if order == 0:
+        out = pred
+        for a, (ax, (u, ok)) in enumerate(zip(geom, coords)):
+            idx = np.clip(np.floor(np.where(ok, u, 0.0) + 0.5).astype(np.int64), 0, ax.count - 1) + ax.lo
+            out = np.take(out, idx, axis=a)
+        return np.ascontiguousarray(np.where(inside, out, np.asarray(default_value).astype(pred.dtype)).astype(pred.dtype))
+    out = pred.astype(np.float32).astype(dtype)
+    for a, (ax, (u, ok)) in enumerate(zip(geom, coords)):
+        u = np.where(ok, u, 0.0)
+        fl = np.floor(u)
+        shape = [1] * pred.ndim
+        shape[a] = ax.n
+        y = (u - fl).astype(dtype).reshape(shape)
+        i = fl.astype(np.int64)
+        lo_tap = np.take(out, np.clip(i, 0, ax.count - 1) + ax.lo, axis=a)
+        hi_tap = np.take(out, np.clip(i + 1, 0, ax.count - 1) + ax.lo, axis=a)
+        out = lo_tap * (dtype(1) - y) + hi_tap * y
+    return np.ascontiguousarray(np.where(inside, out, dtype(default_value)))
+
+
+def _channel_range(channels, Cn: int) -> Tuple[int, int]:
+    """(c0, nsel) of ``channels``: None = all, an int = that channel alone, a (start, stop) pair / range / slice of step 1."""
+    if channels is None:
+        return 0, Cn
+    if isinstance(channels, (int, np.integer)):
+        c0, c1 = int(channels), int(channels) + 1
+    elif isinstance(channels, slice):
+        c0, c1, step = channels.indices(Cn)
+        if step != 1:
+            raise ValueError(f"restore: a contiguous channel range expected, got {channels!r}")
+    elif isinstance(channels, range):
+        if channels.step != 1:
+            raise ValueError(f"restore: a contiguous channel range expected, got {channels!r}")
+        c0, c1 = channels.start, channels.stop
+    else:
+        c0, c1 = (int(v) for v in channels)
+    if not 0 <= c0 < c1 <= Cn:
+        raise ValueError(f"restore: the channel range [{c0}, {c1}) leaves the map's {Cn} channel(s)")
+    return c0, c1 - c0
+
+
+def _restore_device_dtype(dtype, order: int, default_value):
+    """The type the kernel runs a device map of ``dtype`` in.  Order 1 computes in fp32 (float64 is rounded to it, as the numpy path
+    rounds its input).  Order 0 moves values unchanged, so only exact routes are taken: fp32, int16 and int32 as they are, float16 /
+    bfloat16 through fp32, bool / uint8 / int8 through int16 (the result is cast back); float64 and int64 have no exact route and
+    raise, as does an int32 default beyond 2^24 (the C ABI carries the default as a float)."""
+    if order == 1:
+        return torch.float32
+    if dtype in (torch.float32, torch.int16, torch.int32):
+        if dtype == torch.int32 and abs(int(default_value)) > 2 ** 24:
+            raise ValueError(f"restore: an int32 default_value beyond 2^24 in magnitude is not exact on the device path, got {default_value}")
+        return dtype
+    if dtype in (torch.float16, torch.bfloat16):
+        return torch.float32
+    if dtype in (torch.bool, torch.uint8, torch.int8):
+        return torch.int16
+    raise ValueError(f"restore: order 0 keeps every value exactly, and a device map of {dtype} has no exact route through the kernel (fp32, "
+                     "int16, int32 run as they are, float16 / bfloat16 through fp32, bool / uint8 / int8 through int16): cast it first, or "
+                     "hand a numpy array to the host path")
+
+
+def restore(pred, scan_shape, spacing, out_spacing, order=1, channels=None, labels=False, default_value=0, default_label=0):
+    """A map on the network's grid back on the grid of the scan that prepare_scan(raw of ``scan_shape`` at ``spacing``, spacing,
+    out_spacing, img_size = pred's own spatial shape) was given.  ``pred``: (D,H,W), (D,H,W,C) or (B,D,H,W,C).  order 1 (probabilities,
+    entropy): linear, fp32 out; order 0 (candidate and label maps): nearest, dtype kept.  ``channels``: None, an int or a (start, stop)
+    range of the channels to return (for a lesion model, 1 never writes the background at scan resolution).  ``labels``: also return
+    the uint8 argmax over ALL channels of the restored map, ``default_label`` outside -- the probabilities are interpolated and the
+    argmax is taken on the scan's grid; labels are never interpolated.  Returns the map, or (map, labels).
+    numpy in -> restore_host (fp64 compute, fp32 result; dtype kept for order 0); device tensor in -> the kernel of csrc/restore.hip,
+    one launch; for order 0 it keeps dtype and values exactly as the host path does, or raises ValueError for a dtype it has no exact
+    route for (float64, int64: ``_restore_device_dtype``)."""
+    if pred.ndim not in (3, 4, 5):
+        raise ValueError(f"restore: a (D,H,W), (D,H,W,C) or (B,D,H,W,C) map expected, got shape {tuple(pred.shape)}")
+    if order not in (0, 1):
+        raise NotImplementedError(f"restore: order {order!r} is not built; 0 (nearest) and 1 (linear) are")
+    if not 0 <= int(default_label) <= 255:
+        raise ValueError(f"restore: a default label in [0, 255] expected, got {default_label}")
+    spatial = tuple(int(v) for v in (pred.shape[1:4] if pred.ndim == 5 else pred.shape[:3]))
+    Cn = int(pred.shape[-1]) if pred.ndim >= 4 else 1
+    geom = restore_geometry(scan_shape, spacing, out_spacing, spatial)
+    c0, nsel = _channel_range(channels, Cn)
+    if labels and Cn > 255:
+        raise ValueError(f"restore: uint8 labels hold at most 255 channels, got {Cn}")
+    if not isinstance(pred, torch.Tensor):
+        vols = pred if pred.ndim == 5 else pred[None]
+        full = np.stack([restore_host(v, scan_shape, spacing, out_spacing, order, default_value, np.float64) for v in vols])
+        if order == 1:
+            full = full.astype(np.float32)
+        full = full if pred.ndim >= 4 else full[..., None]
+        out = np.ascontiguousarray(full[..., c0:c0 + nsel])
+        lab = np.where(restore_inside(geom), np.argmax(full, axis=-1), int(default_label)).astype(np.uint8) if labels else None
+        if pred.ndim < 5:
+            out, lab = out[0], (lab[0] if labels else None)
+        if pred.ndim == 3:
+            out = out[..., 0]
+        return (out, lab) if labels else out
+    src = pred.to(_restore_device_dtype(pred.dtype, order, default_value))
+    src = src.contiguous().reshape(-1 if pred.ndim == 5 else 1, *spatial, Cn)
+    g = ops.restore_geom(spatial, [ax.n for ax in geom], [ax.ratio for ax in geom], [ax.first for ax in geom],
+                         [ax.count for ax in geom], [ax.lo for ax in geom], order, float(default_value), int(default_label))
+    res = ops.restore(src, g, c0, nsel, True, bool(labels))
+    out, lab = res if labels else (res, None)
+    if order == 0 and out.dtype != pred.dtype:
+        out = out.to(pred.dtype)
+    if pred.ndim < 5:
+        out, lab = out[0], (lab[0] if labels else None)
+    if pred.ndim == 3:
+        out = out[..., 0]
+    return (out, lab) if labels else out

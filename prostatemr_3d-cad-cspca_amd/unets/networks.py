@@ -972,6 +972,38 @@ class M1(LoadableModel):
                         mean, ent = ops.mc_finish(s, n)
                         res.append({"mean": mean, "entropy": ent, **({"samples": draws[j]} if return_samples else {})})
                 return res if casc else res[0]
+
+            def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
+                             **prepare_kw):
+                """From a raw scan to a prediction on the scan's own grid: preprocess.prepare_scan to the model's input size, ``predict``
+                (n_draws == 1) or ``predict_mc``, then preprocess.restore of the result.  ``raw``: (B,d,h,w,C) fp32 / int16 on the
+                device at ``spacing`` (cascaded: the pair or dict of the two stages' scans, both on one grid); ``prepare_kw`` goes to
+                prepare_scan (pad_mode, constant_values, dtype, default_value).  Returns {"mean": (B,d,h,w,nsel) fp32, the channels
+                ``channels`` of the restored softmax [, "entropy": (B,d,h,w) with n_draws > 1] [, "labels": (B,d,h,w) uint8, the argmax
+                of the restored softmax, with ``labels``], "network": what predict / predict_mc returned on the network's grid}; a
+                cascaded model returns [stage 1, stage 2] of these.  Host composition only."""
+                from .. import preprocess as PP
+                casc = outer.references.cascaded != False  # noqa: E712
+                raws = list(outer._cascade_inputs(raw)) if casc else [raw]
+                shape = tuple(int(v) for v in raws[0].shape[1:4])
+                if any(tuple(int(v) for v in r.shape[1:4]) != shape for r in raws):
+                    raise ValueError(f"predict_scan: both stages' scans must share one grid, got {[tuple(r.shape) for r in raws]}")
+                xs = [PP.prepare_scan(r, spacing, out_spacing, outer.input_spatial_dims, percentile=percentile, **prepare_kw)[0]
+                      for r in raws]
+                x = xs if casc else xs[0]
+                net = self.predict(x) if int(n_draws) == 1 else self.predict_mc(x, n_draws, draws_per_pass)
+                res = []
+                for o in (net if casc else [net]):
+                    mean = o["mean"] if isinstance(o, dict) else o
+                    r = PP.restore(mean.contiguous(), shape, spacing, out_spacing, order=1, channels=channels, labels=labels)
+                    d = {"mean": r[0] if labels else r}
+                    if isinstance(o, dict):
+                        d["entropy"] = PP.restore(o["entropy"].unsqueeze(-1), shape, spacing, out_spacing, order=1)[..., 0]
+                    if labels:
+                        d["labels"] = r[1]
+                    d["network"] = o
+                    res.append(d)
+                return res if casc else res[0]
         return _Detect()
 
     # ---- networks.py:209-223 ---------------------------------------------------------------------------------
