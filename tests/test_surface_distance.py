@@ -3,7 +3,10 @@ tests/test_surface_distance_host.py pins against scipy: the shapes, spacings and
 
 Bounds, derived there and not measured here: border masks and every integer count are identical; a distance map is within 1 fp32 ulp
 (the kernels form the same fp64 expression as the restatement: in practice the bits agree); means, percentiles and the hard Dice are
-within rtol 2^-22; NaNs sit in the same places; nsd is exact because no distance lies within 4 fp32 ulp of a tolerance."""
+within rtol 2^-22; NaNs sit in the same places; nsd is exact because no distance lies within 4 fp32 ulp of a tolerance -- which also
+means that `d <= tolerance` and `d < tolerance` count alike here: that the comparison is inclusive is tested in
+tests/test_surface_distance_edges.py (tolerances that are distances of the set), as are the other label sets, percentiles, numbers of
+tolerances, line lengths and block counts than the one point (K = 2, q = 95, T = 4, B = 2, D <= 20) of this module."""
 import functools
 import inspect
 
