@@ -1,8 +1,9 @@
-// dispatch.hip -- the six public conv entry points.  Each builds the logical problem (gather.h) for its role and
-// runs it on the matrix-core kernels when the channel counts allow 16-byte segments, else on the generic
-// direct kernels.  A concat whose members are partly unaligned (the latent z of 1..3 channels in front of the
-// feature map, networks.py:652-653) is split: aligned members -> MFMA, the rest -> direct kernel accumulating
-// into the same output.
+// dispatch.hip -- the public conv entry points.  Each builds the logical problems (gather.h) of its role and runs them on the
+// matrix-core kernels, whatever the channel counts (unaligned members are zero-padded to whole 16-byte K segments inside the
+// kernel); the generic direct kernels take what those kernels decline and are the m1_set_force_direct reference path.
+//   plan_gather    where every sub-problem of a forward / data gradient keeps its panel in `ws`, and when the data gradient is fused
+//   wgrad_ws       the regions of a weight gradient's `ws`
+//   WG_LADDER      the order in which the weight-gradient kernels are tried
 #include "common.h"
 #include "gather.h"
 #include "reduce.h"
@@ -73,6 +74,17 @@ extern "C" int m1_abi_version(void) { return 1; }
 static int g_force_direct = 0;
 extern "C" int m1_set_force_direct(int on) { g_force_direct = on; return M1_OK; }
 
+static inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+static inline unsigned char* at(void* ws, size_t off) { return ws ? (unsigned char*)ws + off : nullptr; }
+
+// matrix-core kernel if not forced direct and supported, else the direct kernel (which needs no workspace)
+static bool use_mfma(const GatherSpec& g) { return !g_force_direct && m1_mfma_supported(g); }
+static size_t gather_ws_bytes(const GatherSpec& g) { return use_mfma(g) ? align256(m1_mfma_ws_bytes(g)) : 0; }
+static int run_gather(const GatherSpec& g, void* ws, int ws_packed, hipStream_t st) {
+    if (!use_mfma(g)) return m1_direct_gather(g, st);
+    return ws ? m1_mfma_gather(g, ws, ws_packed, st) : M1_ERR_WORKSPACE;
+}
+
 // ---- spec builders -------------------------------------------------------------------------------------------
 // forward-type problems: the concat `d->src` is the CONTRACTION axis, `out` has all Cout channels
 static GatherSpec fwd_spec(const m1_conv_desc_t* d, bool T, const float* w, const float* bias, void* y) {
@@ -101,18 +113,6 @@ static GatherSpec dgrad_spec(const m1_conv_desc_t* d, bool T, const float* w, co
 // the data gradient of ALL concat members as one problem: Cin output columns spread over the members' gradient tensors
 // (GatherSpec::outs).  One launch instead of one per member: dY is gathered once per tile instead of once per member, 32-channel
 // members stop running on 32-column tiles (the loader-bound shape), and a 5-member dense-skip concat costs 1 launch, not 5.
-static bool dgrad_fused_ok(const m1_conv_desc_t* d) {
-    int en = M1_CFG("M1_DGRAD_FUSED", 1);
-    if (!en || d->nsrc < 2) return false;
-    const int seg = d->dtype == M1_BF16 ? 8 : 4;
-    for (int i = 0; i < d->nsrc; ++i) if (d->src[i].C % seg) return false;
-    // the wide, shallow layers (res0/res1: <= 64 dY channels, stride 1, >= 32,768 voxels) run on the halo-tile kernel, whose blocks
-    // own one 32-column weight slice each: per-member launches are faster there (192->32 at res0: 0.76 vs 1.13 ms per step fused)
-    const long long vox = (long long)d->N * d->D * d->H * d->W;
-    int hf = M1_CFG("M1_DGRAD_FUSED_HALO", 0);
-    if (!hf && d->dtype == M1_BF16 && d->Cout <= 64 && d->sd == 1 && d->sh == 1 && d->sw == 1 && vox >= 32768 && d->kd * d->kh * d->kw > 1) return false;
-    return true;
-}
 static GatherSpec dgrad_fused_spec(const m1_conv_desc_t* d, bool T, const float* w, const void* dy, void* const* dx, const int* accumulate) {
     GatherSpec g = dgrad_spec(d, T, w, dy, nullptr, 0, 0);
     g.OC = d->Cin; g.oc_off = 0; g.out = nullptr; g.accumulate = 0;
@@ -122,46 +122,30 @@ static GatherSpec dgrad_fused_spec(const m1_conv_desc_t* d, bool T, const float*
     }
     return g;
 }
-
-static inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-// Every channel count runs on the matrix-core kernels (unaligned members are zero-padded to whole 16-byte K
-// segments inside the kernel); the generic direct kernels remain as the m1_set_force_direct reference path.
-static void split_members(const GatherSpec& g, GatherSpec* mf, GatherSpec* dr) {
-    *mf = g; *dr = g; mf->nsrc = 0; dr->nsrc = 0;
-    if (g_force_direct || !m1_mfma_supported(g)) { *dr = g; return; }
-    *mf = g;
+static bool dgrad_fused(const m1_conv_desc_t* d, bool T) {
+    int en = M1_CFG("M1_DGRAD_FUSED", 1);
+    if (!en || d->nsrc < 2) return false;
+    const int seg = d->dtype == M1_BF16 ? 8 : 4;
+    for (int i = 0; i < d->nsrc; ++i) if (d->src[i].C % seg) return false;
+    // the wide, shallow layers (res0/res1: <= 64 dY channels, stride 1, >= 32,768 voxels) run on the halo-tile kernel, whose blocks
+    // own one 32-column weight slice each: per-member launches are faster there (192->32 at res0: 0.76 vs 1.13 ms per step fused)
+    const long long vox = (long long)d->N * d->D * d->H * d->W;
+    int hf = M1_CFG("M1_DGRAD_FUSED_HALO", 0);
+    if (!hf && d->dtype == M1_BF16 && d->Cout <= 64 && d->sd == 1 && d->sh == 1 && d->sw == 1 && vox >= 32768 && d->kd * d->kh * d->kw > 1) return false;
+    return use_mfma(dgrad_fused_spec(d, T, nullptr, nullptr, nullptr, nullptr));
 }
 
-static size_t gather_ws_bytes(const GatherSpec& g) {
-    GatherSpec mf, dr; split_members(g, &mf, &dr);
-    return mf.nsrc ? align256(m1_mfma_ws_bytes(mf)) : 0;
-}
-
-static int run_gather(const GatherSpec& g, void* ws, int ws_packed, hipStream_t st) {
-    GatherSpec mf, dr; split_members(g, &mf, &dr);
-    int rc = M1_OK;
-    if (mf.nsrc) {
-        if (!ws) return M1_ERR_WORKSPACE;
-        rc = m1_mfma_gather(mf, ws, ws_packed, st); if (rc) return rc;
-        if (dr.nsrc) { dr.accumulate = 1; dr.bias = nullptr; rc = m1_direct_gather(dr, st); }
-        return rc;
-    }
-    return m1_direct_gather(dr, st);
-}
-
-// ---- forward of a wide concat as one halo-tile launch per member group ----------------------------------------------
-// The halo-tile kernel (conv_halo.hip) stages an input tile once for all taps but holds at most 64 contraction channels; the
-// dense-skip concats of the full model (160 channels at res0, 256 at res1: networks.py:604-623) fell back to the per-tap
-// gather (160->32 at res0: 470 us, bound by 9x re-reads from L2).  Split the members into groups of 8/16/32/64 channels: the
-// first group writes y (+ bias), the others add into it in their epilogue, the last one also emits the InstanceNorm statistics
-// of the sum.  Each group is an ordinary conv over its members with a channel offset into the weights (own panel, own job).
-struct FwdGroups { int n; int first[M1_MAX_SRC], count[M1_MAX_SRC], coff[M1_MAX_SRC]; bool T; };
+// ---- the plan of a forward / data gradient: its sub-problems and their places in the workspace ------------------------------
+// One sub-problem of a forward (concat members [first, first + count) at channel ch_off of the contraction) or of a data gradient
+// (the gradient of those members), and where its panel lives in `ws`.
+struct GatherItem { int first, count, ch_off; size_t off, bytes; };
+struct GatherPlan { bool T, fused; int n; GatherItem item[M1_MAX_SRC]; size_t stats_off, total; };
+static void add_item(GatherPlan* p, int first, int count, int ch_off) { p->item[p->n++] = GatherItem{first, count, ch_off, 0, 0}; }
 // A concat of wide members plus a tiny one that is not a whole 16-byte segment per voxel (the latent z of 1..3 channels in front of
 // the feature map: networks.py:652-653, dec_hi = Conv3DTranspose([z, f])): as ONE problem the odd member takes the whole contraction
 // off the LDS-DMA loader (515 -> 256 at res4: 144 us against 69 us for 512 -> 256).  Split: the run of 64-byte-aligned members is one
 // conv that writes y (+ bias) on the fast path, the odd members follow as tiny convs that add into y.  Forward and transposed forward.
-static bool odd_split(const m1_conv_desc_t* d, bool T, FwdGroups* fg) {
+static bool odd_split(const m1_conv_desc_t* d, GatherPlan* p) {
     int en = M1_CFG("M1_ODD_SPLIT", 1);
     if (!en || g_force_direct || d->nsrc < 2) return false;
     const int seg = d->dtype == M1_BF16 ? 8 : 4, chunk = 4 * seg;
@@ -174,40 +158,83 @@ static bool odd_split(const m1_conv_desc_t* d, bool T, FwdGroups* fg) {
     }
     if (!nodd || a0 < 0 || call < 64) return false;
     for (int i = a0; i <= a1; ++i) if (d->src[i].C % chunk) return false;        // the aligned members must be one run
-    fg->n = 0; fg->T = T;
     int off = 0, offs[M1_MAX_SRC];
     for (int i = 0; i < d->nsrc; ++i) { offs[i] = off; off += d->src[i].C; }
-    fg->first[0] = a0; fg->count[0] = a1 - a0 + 1; fg->coff[0] = offs[a0]; fg->n = 1;
-    if (a0 > 0) { fg->first[fg->n] = 0; fg->count[fg->n] = a0; fg->coff[fg->n] = 0; fg->n++; }
-    if (a1 + 1 < d->nsrc) { fg->first[fg->n] = a1 + 1; fg->count[fg->n] = d->nsrc - a1 - 1; fg->coff[fg->n] = offs[a1 + 1]; fg->n++; }
+    p->n = 0;
+    add_item(p, a0, a1 - a0 + 1, offs[a0]);
+    if (a0 > 0) add_item(p, 0, a0, 0);
+    if (a1 + 1 < d->nsrc) add_item(p, a1 + 1, d->nsrc - a1 - 1, offs[a1 + 1]);
     return true;
 }
-static bool fwd_groups(const m1_conv_desc_t* d, bool T, FwdGroups* fg) {
-    if (odd_split(d, T, fg)) return true;
-    fg->T = T;
+// Forward of a wide concat as one halo-tile launch per member group.  The halo-tile kernel (conv_halo.hip) stages an input tile
+// once for all taps but holds at most 64 contraction channels; the dense-skip concats of the full model (160 channels at res0, 256
+// at res1: networks.py:604-623) fell back to the per-tap gather (160->32 at res0: 470 us, bound by 9x re-reads from L2).  Split the
+// members into groups of 8/16/32/64 channels: the first group writes y (+ bias), the others add into it in their epilogue, the last
+// one also emits the InstanceNorm statistics of the sum.  Each group is an ordinary conv over its members with a channel offset
+// into the weights (own panel, own job).
+static bool fwd_groups(const m1_conv_desc_t* d, GatherPlan* p) {
+    if (odd_split(d, p)) return true;
+    const bool T = p->T;
     int en = M1_CFG("M1_HALO_GROUPS", 1);
     if (!en || T || g_force_direct || d->dtype != M1_BF16 || d->nsrc < 2 || d->Cin <= 64) return false;
     if (d->kd * d->kh * d->kw < 2) return false;
     Geo q = conv_geo(d);
     if (q.OW % 8 || (long long)d->N * q.OD * q.OH * q.OW < 32768) return false;
     auto ok = [](int c) { return c == 8 || c == 16 || c == 32 || c == 64; };
-    fg->n = 0; int cur = 0, off = 0;
+    p->n = 0; int cur = 0, off = 0;
     for (int i = 0; i < d->nsrc; ++i) {
         const int c = d->src[i].C;
         if (!ok(c)) return false;
-        if (fg->n > 0 && ok(cur + c) && cur + c <= 64) { fg->count[fg->n - 1]++; cur += c; }
-        else { fg->first[fg->n] = i; fg->count[fg->n] = 1; fg->coff[fg->n] = off; fg->n++; cur = c; }
+        if (p->n > 0 && ok(cur + c) && cur + c <= 64) { p->item[p->n - 1].count++; cur += c; }
+        else { add_item(p, i, 1, off); cur = c; }
         off += c;
     }
-    return fg->n >= 2;
+    return p->n >= 2;
 }
-static GatherSpec fwd_group_spec(const m1_conv_desc_t* d, const FwdGroups& fg, int gi, const float* w, const float* bias, void* y) {
-    GatherSpec g = fwd_spec(d, fg.T, w, gi == 0 ? bias : nullptr, y);
-    g.nsrc = fg.count[gi];
-    for (int i = 0; i < g.nsrc; ++i) { g.src[i] = d->src[fg.first[gi] + i].ptr; g.srcC[i] = d->src[fg.first[gi] + i].C; }
-    g.cc_off = fg.coff[gi];
-    g.accumulate = gi > 0 ? 1 : 0;
+// item k of a forward plan: the first writes y (+ bias), the others add into it (an ungrouped forward is its only item)
+static GatherSpec fwd_item_spec(const m1_conv_desc_t* d, const GatherPlan& p, int k, const float* w, const float* bias, void* y) {
+    const GatherItem& it = p.item[k];
+    GatherSpec g = fwd_spec(d, p.T, w, k == 0 ? bias : nullptr, y);
+    g.nsrc = it.count;
+    for (int i = 0; i < g.nsrc; ++i) { g.src[i] = d->src[it.first + i].ptr; g.srcC[i] = d->src[it.first + i].C; }
+    g.cc_off = it.ch_off;
+    g.accumulate = k > 0 ? 1 : 0;
     return g;
+}
+// item k of a data-gradient plan: all members as one problem (fused) or member it.first alone
+static GatherSpec dgrad_item_spec(const m1_conv_desc_t* d, const GatherPlan& p, int k, const float* w, const void* dy, void* const* dx,
+                                  const int* accumulate) {
+    if (p.fused) return dgrad_fused_spec(d, p.T, w, dy, dx, accumulate);
+    const int i = p.item[k].first;
+    GatherSpec g = dgrad_spec(d, p.T, w, dy, dx ? dx[i] : nullptr, i, p.item[k].ch_off);
+    g.accumulate = accumulate && accumulate[i] ? 1 : 0;
+    return g;
+}
+// THE layout of a forward (role 0) / data-gradient (role 1) workspace: the panels of the sub-problems back to back, in the order they
+// run; behind them the statistics rows of a forward; 256 spare bytes.  A sub-problem the direct kernels take has no panel (0 bytes).
+static GatherPlan plan_gather(const m1_conv_desc_t* d, bool T, int role) {
+    GatherPlan p{}; p.T = T;
+    if (role == 0) {
+        if (!fwd_groups(d, &p)) { p.n = 0; add_item(&p, 0, d->nsrc, 0); }
+    } else if (dgrad_fused(d, T)) {
+        p.fused = true; add_item(&p, 0, d->nsrc, 0);
+    } else {
+        for (int i = 0, off = 0; i < d->nsrc; ++i) { add_item(&p, i, 1, off); off += d->src[i].C; }
+    }
+    size_t off = 0;
+    for (int k = 0; k < p.n; ++k) {
+        p.item[k].off = off;
+        p.item[k].bytes = gather_ws_bytes(role == 0 ? fwd_item_spec(d, p, k, nullptr, nullptr, nullptr)
+                                                    : dgrad_item_spec(d, p, k, nullptr, nullptr, nullptr, nullptr));
+        off += p.item[k].bytes;
+    }
+    p.stats_off = off;
+    if (role == 0) {
+        const Geo q = T ? convT_geo(d) : conv_geo(d);
+        off += align256(m1_stats_ws_floats(d->N, (long long)q.OD * q.OH * q.OW, d->Cout) * sizeof(float));
+    }
+    p.total = off + 256;
+    return p;
 }
 
 // ---- stem weight gradient (Cin < 8: the image channels, networks.py:472) -----------------------------------------------
@@ -219,10 +246,6 @@ static bool stem_wanted(const m1_conv_desc_t* d, bool T) {
     int en = M1_CFG("M1_STEM_TF", 1);
     // (fp32: the same with 4 channels = one 16-byte segment per voxel, on the fp32 tap-fused kernel)
     return en && !T && !g_force_direct && d->nsrc == 1 && d->src[0].C < (d->dtype == M1_BF16 ? 8 : 4) && d->Cin == d->src[0].C;
-}
-static size_t stem_ws_bytes(const m1_conv_desc_t* d, bool T) {
-    if (!stem_wanted(d, T)) return 0;
-    return align256((size_t)d->N * d->D * d->H * d->W * 8 * 2) + align256((size_t)d->kd * d->kh * d->kw * 8 * d->Cout * sizeof(float));
 }
 // Zero fill as a KERNEL.  hipMemsetAsync on a capturing stream becomes a memset node of the step's hipGraph, and on this ROCm release
 // a replayed graph does not keep a memset node ordered between the kernel nodes around it (round 5: from the third replay on, the
@@ -295,64 +318,39 @@ static size_t wgrad_rx_bytes(const m1_conv_desc_t* d) {
     if (b < 2 * stride * sizeof(float)) b = 2 * stride * sizeof(float);
     return align256(b);
 }
-// every concat member has a region of its own (wgrad_rx_bytes each): with deferred folds (m1_wgrad_defer) the copies of
-// member i must survive the kernels of member i+1
-static size_t wgrad_rx_total(const m1_conv_desc_t* d) { return wgrad_rx_bytes(d) * (size_t)(d->nsrc > 0 ? d->nsrc : 1); }
+// THE layout of a weight-gradient workspace (byte offsets): the reduction scratch of the bias gradient, the stem's padded input x8
+// and scratch gradient r8 (stem_wanted only), then one partial-copy region of rx_floats per concat member: with deferred folds
+// (m1_wgrad_defer) the copies of member i must survive the kernels of member i+1.
+struct WgradWs { size_t reduce_bytes, x8, r8, rx, total; long long rx_floats; };
+static WgradWs wgrad_ws(const m1_conv_desc_t* d, bool T) {
+    const Geo q = T ? convT_geo(d) : conv_geo(d);
+    WgradWs w{};
+    w.reduce_bytes = align256(m1_reduce_ws_floats(d->N, (long long)q.OD * q.OH * q.OW, d->Cout, 1) * sizeof(float)) + 256;
+    w.x8 = w.r8 = w.rx = w.reduce_bytes;
+    if (stem_wanted(d, T)) {                             // x8: 16 bytes per voxel; r8: 8 input rows per tap (fp32 uses 4 of them)
+        w.r8 = w.x8 + align256((size_t)d->N * d->D * d->H * d->W * 16);
+        w.rx = w.r8 + align256((size_t)d->kd * d->kh * d->kw * 8 * d->Cout * sizeof(float));
+    }
+    const size_t rx_bytes = wgrad_rx_bytes(d);
+    w.rx_floats = (long long)(rx_bytes / sizeof(float));
+    w.total = w.rx + rx_bytes * (size_t)d->nsrc;
+    return w;
+}
 
 // ---- workspace query ---------------------------------------------------------------------------------------------
 extern "C" size_t m1_conv_ws_bytes(const m1_conv_desc_t* d, int transposed, int role) {
     if (!desc_ok(d)) return 0;
-    const bool T = transposed != 0;
-    if (role == 0) {
-        Geo q0 = T ? convT_geo(d) : conv_geo(d);
-        size_t panels = 0;
-        FwdGroups fg;
-        if (fwd_groups(d, T, &fg)) { for (int gi = 0; gi < fg.n; ++gi) panels += gather_ws_bytes(fwd_group_spec(d, fg, gi, nullptr, nullptr, nullptr)); }
-        else panels = gather_ws_bytes(fwd_spec(d, T, nullptr, nullptr, nullptr));
-        return panels + align256(m1_stats_ws_floats(d->N, (long long)q0.OD * q0.OH * q0.OW, d->Cout) * sizeof(float)) + 256;
-    }
-    if (role == 1) {
-        if (dgrad_fused_ok(d) && !g_force_direct && m1_mfma_supported(dgrad_fused_spec(d, T, nullptr, nullptr, nullptr, nullptr)))
-            return gather_ws_bytes(dgrad_fused_spec(d, T, nullptr, nullptr, nullptr, nullptr)) + 256;
-        size_t m = 0; int off = 0;
-        for (int i = 0; i < d->nsrc; ++i) {
-            m += gather_ws_bytes(dgrad_spec(d, T, nullptr, nullptr, nullptr, i, off));
-            off += d->src[i].C;
-        }
-        return m + 256;
-    }
-    Geo q = T ? convT_geo(d) : conv_geo(d);
-    return align256(m1_reduce_ws_floats(d->N, (long long)q.OD * q.OH * q.OW, d->Cout, 1) * sizeof(float)) + 256 + stem_ws_bytes(d, T) +
-           wgrad_rx_total(d);
+    return role == 0 || role == 1 ? plan_gather(d, transposed != 0, role).total : wgrad_ws(d, transposed != 0).total;
 }
 
 // ---- packed-weight panel records ----------------------------------------------------------------------------------
-// Device addresses of the pack-job records inside `ws` (one per matrix-core panel: role 0 -> 1, role 1 -> one per
-// concat member).  A record is filled by the first (lazy) pack of its panel; m1_pack_batch re-runs filled records.
+// Device addresses of the pack-job records inside `ws`: one per matrix-core panel of the role's plan.  A record is filled by the
+// first (lazy) pack of its panel; m1_pack_batch re-runs filled records.
 extern "C" int m1_conv_pack_jobs(const m1_conv_desc_t* d, int transposed, int role, void* ws, void** jobs_out) {
-    if (!desc_ok(d) || !ws || !jobs_out) return 0;
-    const bool T = transposed != 0;
+    if (!desc_ok(d) || !ws || !jobs_out || (role != 0 && role != 1)) return 0;
+    const GatherPlan p = plan_gather(d, transposed != 0, role);
     int n = 0;
-    if (role == 0) {
-        FwdGroups fg;
-        if (fwd_groups(d, T, &fg)) {
-            size_t woff = 0;
-            for (int gi = 0; gi < fg.n; ++gi) {
-                const size_t b = gather_ws_bytes(fwd_group_spec(d, fg, gi, nullptr, nullptr, nullptr));
-                if (b) jobs_out[n++] = (unsigned char*)ws + woff;
-                woff += b;
-            }
-        } else if (gather_ws_bytes(fwd_spec(d, T, nullptr, nullptr, nullptr))) jobs_out[n++] = ws;
-    } else if (role == 1 && dgrad_fused_ok(d) && !g_force_direct && m1_mfma_supported(dgrad_fused_spec(d, T, nullptr, nullptr, nullptr, nullptr))) {
-        if (gather_ws_bytes(dgrad_fused_spec(d, T, nullptr, nullptr, nullptr, nullptr))) jobs_out[n++] = ws;
-    } else if (role == 1) {
-        int off = 0; size_t woff = 0;
-        for (int i = 0; i < d->nsrc; ++i) {
-            const size_t b = gather_ws_bytes(dgrad_spec(d, T, nullptr, nullptr, nullptr, i, off));
-            if (b) jobs_out[n++] = (unsigned char*)ws + woff;
-            woff += b; off += d->src[i].C;
-        }
-    }
+    for (int k = 0; k < p.n; ++k) if (p.item[k].bytes) jobs_out[n++] = at(ws, p.item[k].off);
     return n;
 }
 extern "C" int m1_pack_batch(const void* const* jobs_dev, const int* block_prefix_dev, int njobs, int total_blocks, void* stream) {
@@ -363,39 +361,31 @@ extern "C" int m1_pack_batch(const void* const* jobs_dev, const int* block_prefi
 }
 
 // ---- Conv3D ------------------------------------------------------------------------------------------------------
+// the items of the forward plan in order; the last one also emits the InstanceNorm statistics of the finished y
+static int fwd_common(const m1_conv_desc_t* d, bool T, const float* w, const float* bias, void* y, float* stats, void* ws, int ws_packed,
+                      hipStream_t st) {
+    if (stats && !ws) return M1_ERR_WORKSPACE;
+    const GatherPlan p = plan_gather(d, T, 0);
+    // without a workspace there are no groups: the whole concat as one problem (the direct kernels take it, or M1_ERR_WORKSPACE)
+    if (!ws && p.n > 1) return run_gather(fwd_spec(d, T, w, bias, y), nullptr, ws_packed, st);
+    for (int k = 0; k < p.n; ++k) {
+        GatherSpec g = fwd_item_spec(d, p, k, w, bias, y);
+        const bool emit = stats && k == p.n - 1;
+        if (emit) { g.stats_out = stats; g.stats_eps = 1e-3f; g.stats_ws = reinterpret_cast<float*>(at(ws, p.stats_off)); }   // tfa InstanceNormalization epsilon
+        int rc = run_gather(g, at(ws, p.item[k].off), ws_packed, st); if (rc) return rc;
+        // direct path: conv, then the stand-alone reduction.  (Known gap, kept as it was: a GROUPED forward that the matrix-core
+        // kernels decline -- more than 27 taps -- runs its groups on the direct kernels and writes no statistics.)
+        if (emit && p.n == 1 && !use_mfma(g))
+            return m1_stats_internal(y, d->N, (long long)g.OD * g.OH * g.OW, d->Cout, d->dtype, 1e-3f, stats, g.stats_ws, st);
+    }
+    return M1_OK;
+}
 extern "C" int m1_conv3d_fwd(const m1_conv_desc_t* d, const float* w, const float* bias, void* y, float* stats, void* ws,
                              int ws_packed, void* stream) {
     if (m1_debug_skip("conv_fwd")) return M1_OK;
     if (!desc_ok(d) || !w || !y) return M1_ERR_BAD_ARG;
     M1ProfScope ps(prof_name("conv3d_fwd", d).s, 2.0 * conv_macs(d, false), conv_bytes(d, false), (hipStream_t)stream);
-    FwdGroups fg;
-    if (ws && fwd_groups(d, false, &fg)) {
-        size_t woff = 0, total = 0;
-        for (int gi = 0; gi < fg.n; ++gi) total += gather_ws_bytes(fwd_group_spec(d, fg, gi, nullptr, nullptr, nullptr));
-        for (int gi = 0; gi < fg.n; ++gi) {
-            GatherSpec gg = fwd_group_spec(d, fg, gi, w, bias, y);
-            if (stats && gi == fg.n - 1) {
-                gg.stats_out = stats; gg.stats_eps = 1e-3f;
-                gg.stats_ws = reinterpret_cast<float*>((unsigned char*)ws + total);
-            }
-            int rc = run_gather(gg, (unsigned char*)ws + woff, ws_packed, (hipStream_t)stream); if (rc) return rc;
-            woff += gather_ws_bytes(gg);
-        }
-        return M1_OK;
-    }
-    GatherSpec g = fwd_spec(d, false, w, bias, y);
-    if (stats) {
-        if (!ws) return M1_ERR_WORKSPACE;
-        g.stats_out = stats; g.stats_eps = 1e-3f;        // tfa InstanceNormalization epsilon
-        g.stats_ws = reinterpret_cast<float*>((unsigned char*)ws + gather_ws_bytes(g));
-        GatherSpec mf, dr; split_members(g, &mf, &dr);
-        if (!mf.nsrc) {                                   // direct path: conv, then the stand-alone reduction
-            int rc = m1_direct_gather(dr, (hipStream_t)stream); if (rc) return rc;
-            Geo q = conv_geo(d);
-            return m1_stats_internal(y, d->N, (long long)q.OD * q.OH * q.OW, d->Cout, d->dtype, 1e-3f, stats, g.stats_ws, (hipStream_t)stream);
-        }
-    }
-    return run_gather(g, ws, ws_packed, (hipStream_t)stream);
+    return fwd_common(d, false, w, bias, y, stats, ws, ws_packed, (hipStream_t)stream);
 }
 // ---- conv1 || conv4 of an SE block (network_blocks.py:53,64: same input, same kernel size and strides) as ONE problem --------
 // Forward: one conv with C1 + C4 output columns, written to two tensors ([y1 | y4]) with their own bias vectors and InstanceNorm
@@ -403,28 +393,50 @@ extern "C" int m1_conv3d_fwd(const m1_conv_desc_t* d, const float* w, const floa
 // tile ride on the 128-column tiles of their big twin.  Data gradient: one contraction over the virtual concat [dy1 | dy4] with a
 // panel packed from both weight tensors (no read-modify-write of dx by a second launch).  d->Cout = C1 + C4.
 static bool pair_ok(const m1_conv_desc_t* d, int C1) {
+    if (!desc_ok(d) || g_force_direct) return false;     // (desc_ok: d may be null)
     const int seg = d->dtype == M1_BF16 ? 8 : 4;
-    if (!desc_ok(d) || C1 <= 0 || C1 >= d->Cout || C1 % seg || (d->Cout - C1) % seg || g_force_direct) return false;
+    if (C1 <= 0 || C1 >= d->Cout || C1 % seg || (d->Cout - C1) % seg) return false;
     for (int i = 0; i < d->nsrc; ++i) if (d->src[i].C % seg) return false;
     return true;
+}
+// The pair's problems live in the workspace of the plain conv with C1 + C4 outputs (the caller sizes `ws` from d): one item of that
+// conv's plan, with the second weight tensor added.  false: not as a pair (the shape runs as a grouped forward / a data gradient
+// per member, or the matrix-core kernel does not take it).  The pointers may be null (m1_conv3d_pair_supported).
+static bool pair_fwd_spec(const m1_conv_desc_t* d, int C1, const float* w1, const float* b1, const float* w4, const float* b4, void* y1,
+                          void* y4, float* stats1, float* stats4, void* ws, GatherSpec* out) {
+    const GatherPlan p = plan_gather(d, false, 0);
+    if (p.n != 1) return false;
+    const int C4 = d->Cout - C1;
+    GatherSpec g = fwd_item_spec(d, p, 0, w1, b1, nullptr);
+    g.wST = (long long)d->Cin * C1; g.wSC = C1; g.wSO = 1;
+    g.w2 = w4; g.w2ST = (long long)d->Cin * C4; g.w2SC = C4; g.w2SO = 1; g.oc_split = C1; g.bias2 = b4;
+    g.nout = 2; g.outs[0] = y1; g.outC[0] = C1; g.outAcc[0] = 0; g.outs[1] = y4; g.outC[1] = C4; g.outAcc[1] = 0;
+    if (stats1) { g.stats_out = stats1; g.stats_out2 = stats4; g.stats_eps = 1e-3f; g.stats_ws = reinterpret_cast<float*>(at(ws, p.stats_off)); }
+    *out = g;
+    return m1_mfma_supported(g) && gather_ws_bytes(g) == p.item[0].bytes;      // (the statistics rows start behind the pair's panel)
+}
+static bool pair_dgrad_spec(const m1_conv_desc_t* d, int C1, const float* w1, const float* w4, const void* dy1, const void* dy4,
+                            void* const* dx, const int* accumulate, GatherSpec* out) {
+    const GatherPlan p = plan_gather(d, false, 1);
+    if (p.n != 1) return false;
+    const int C4 = d->Cout - C1;
+    GatherSpec g = dgrad_item_spec(d, p, 0, w1, dy1, dx, accumulate);
+    g.nsrc = 2; g.src[0] = dy1; g.srcC[0] = C1; g.src[1] = dy4; g.srcC[1] = C4;
+    g.wST = (long long)d->Cin * C1; g.wSC = 1; g.wSO = C1;
+    g.w2 = w4; g.w2ST = (long long)d->Cin * C4; g.w2SC = 1; g.w2SO = C4; g.c_split = C1;
+    *out = g;
+    // The pair's panel must FIT the plan's (nothing of a data-gradient workspace lies behind it).  Equal it need not be: the plan
+    // sizes for dy as one tensor of C1 + C4 channels, and conv_t3's 32-channel rule may hold for that sum but not for C1 and C4
+    // (48 + 144): the plan then also sizes for a kernel that the pair does not take.
+    return m1_mfma_supported(g) && gather_ws_bytes(g) <= p.item[0].bytes;
 }
 extern "C" int m1_conv3d_pair_fwd(const m1_conv_desc_t* d, const float* w1, const float* b1, const float* w4, const float* b4, int C1,
                                   void* y1, void* y4, float* stats1, float* stats4, void* ws, int ws_packed, void* stream) {
     if (m1_debug_skip("conv_fwd")) return M1_OK;
     if (!d || !w1 || !w4 || !y1 || !y4 || !ws || (stats1 == nullptr) != (stats4 == nullptr)) return M1_ERR_BAD_ARG;
-    FwdGroups fg;
-    if (!pair_ok(d, C1) || fwd_groups(d, false, &fg)) return M1_ERR_UNSUPPORTED;
+    GatherSpec g;
+    if (!pair_ok(d, C1) || !pair_fwd_spec(d, C1, w1, b1, w4, b4, y1, y4, stats1, stats4, ws, &g)) return M1_ERR_UNSUPPORTED;
     M1ProfScope ps(prof_name("conv3d_fwd", d).s, 2.0 * conv_macs(d, false), conv_bytes(d, false), (hipStream_t)stream);
-    const int C4 = d->Cout - C1;
-    GatherSpec g = fwd_spec(d, false, w1, b1, nullptr);
-    g.wST = (long long)d->Cin * C1; g.wSC = C1; g.wSO = 1;
-    g.w2 = w4; g.w2ST = (long long)d->Cin * C4; g.w2SC = C4; g.w2SO = 1; g.oc_split = C1; g.bias2 = b4;
-    g.nout = 2; g.outs[0] = y1; g.outC[0] = C1; g.outAcc[0] = 0; g.outs[1] = y4; g.outC[1] = C4; g.outAcc[1] = 0;
-    if (!m1_mfma_supported(g)) return M1_ERR_UNSUPPORTED;
-    if (stats1) {
-        g.stats_out = stats1; g.stats_out2 = stats4; g.stats_eps = 1e-3f;
-        g.stats_ws = reinterpret_cast<float*>((unsigned char*)ws + gather_ws_bytes(g));
-    }
     return m1_mfma_gather(g, ws, ws_packed, (hipStream_t)stream);
 }
 extern "C" int m1_conv3d_pair_dgrad(const m1_conv_desc_t* d, const float* w1, const float* w4, int C1, const void* dy1, const void* dy4,
@@ -433,20 +445,9 @@ extern "C" int m1_conv3d_pair_dgrad(const m1_conv_desc_t* d, const float* w1, co
     if (!d || !w1 || !w4 || !dy1 || !dy4 || !dx || !ws) return M1_ERR_BAD_ARG;
     if (!pair_ok(d, C1)) return M1_ERR_UNSUPPORTED;
     M1ProfScope ps(prof_name("conv3d_dgrad", d).s, 2.0 * conv_macs(d, false), conv_bytes(d, false), (hipStream_t)stream);
-    const int C4 = d->Cout - C1;
+    if (d->nsrc == 1 && !dx[0]) return M1_OK;             // (a single unwanted gradient is answered before the shape is judged)
     GatherSpec g;
-    if (d->nsrc >= 2) {
-        if (!dgrad_fused_ok(d)) return M1_ERR_UNSUPPORTED;
-        g = dgrad_fused_spec(d, false, w1, dy1, dx, accumulate);
-    } else {
-        g = dgrad_spec(d, false, w1, dy1, dx[0], 0, 0);
-        g.accumulate = accumulate && accumulate[0] ? 1 : 0;
-        if (!dx[0]) return M1_OK;
-    }
-    g.nsrc = 2; g.src[0] = dy1; g.srcC[0] = C1; g.src[1] = dy4; g.srcC[1] = C4;
-    g.wST = (long long)d->Cin * C1; g.wSC = 1; g.wSO = C1;
-    g.w2 = w4; g.w2ST = (long long)d->Cin * C4; g.w2SC = 1; g.w2SO = C4; g.c_split = C1;
-    if (!m1_mfma_supported(g)) return M1_ERR_UNSUPPORTED;
+    if (!pair_dgrad_spec(d, C1, w1, w4, dy1, dy4, dx, accumulate, &g)) return M1_ERR_UNSUPPORTED;
     bool any = false;
     for (int i = 0; i < d->nsrc; ++i) any |= dx[i] != nullptr;
     return any ? m1_mfma_gather(g, ws, ws_packed, (hipStream_t)stream) : M1_OK;
@@ -454,22 +455,11 @@ extern "C" int m1_conv3d_pair_dgrad(const m1_conv_desc_t* d, const float* w1, co
 
 // 1 when BOTH m1_conv3d_pair_fwd and m1_conv3d_pair_dgrad take this shape (neither would return M1_ERR_UNSUPPORTED): the caller
 // decides between the pair and the two single convs BEFORE it builds its autograd graph (a refusal in the middle of a backward pass
-// has no fallback).  Mirrors every gate of the two entry points.
+// has no fallback).  The same gates as the two entry points: pair_ok and their spec builders.
 extern "C" int m1_conv3d_pair_supported(const m1_conv_desc_t* d, int C1) {
-    if (!d || g_force_direct) return 0;
-    FwdGroups fg;
-    if (!pair_ok(d, C1) || fwd_groups(d, false, &fg)) return 0;
-    const int C4 = d->Cout - C1;
-    GatherSpec g = fwd_spec(d, false, nullptr, nullptr, nullptr);
-    g.oc_split = C1; g.nout = 2; g.outC[0] = C1; g.outC[1] = C4;
-    if (!m1_mfma_supported(g)) return 0;
-    GatherSpec q;
-    if (d->nsrc >= 2) {
-        if (!dgrad_fused_ok(d)) return 0;
-        q = dgrad_fused_spec(d, false, nullptr, nullptr, nullptr, nullptr);
-    } else q = dgrad_spec(d, false, nullptr, nullptr, nullptr, 0, 0);
-    q.nsrc = 2; q.srcC[0] = C1; q.srcC[1] = C4; q.c_split = C1;
-    return m1_mfma_supported(q) ? 1 : 0;
+    GatherSpec g;
+    return pair_ok(d, C1) && pair_fwd_spec(d, C1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g) &&
+           pair_dgrad_spec(d, C1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g);
 }
 
 extern "C" int m1_convT3d_fwd(const m1_conv_desc_t* d, const float* w, const float* bias, void* y, void* ws, int ws_packed,
@@ -477,37 +467,18 @@ extern "C" int m1_convT3d_fwd(const m1_conv_desc_t* d, const float* w, const flo
     if (m1_debug_skip("conv_fwd")) return M1_OK;
     if (!desc_ok(d) || !w || !y) return M1_ERR_BAD_ARG;
     M1ProfScope ps(prof_name("convT3d_fwd", d).s, 2.0 * conv_macs(d, true), conv_bytes(d, true), (hipStream_t)stream);
-    FwdGroups fg;
-    if (ws && fwd_groups(d, true, &fg)) {                 // (odd_split: the aligned run first, the tiny members add into y)
-        size_t woff = 0;
-        for (int gi = 0; gi < fg.n; ++gi) {
-            GatherSpec gg = fwd_group_spec(d, fg, gi, w, bias, y);
-            int rc = run_gather(gg, (unsigned char*)ws + woff, ws_packed, (hipStream_t)stream); if (rc) return rc;
-            woff += gather_ws_bytes(gg);
-        }
-        return M1_OK;
-    }
-    return run_gather(fwd_spec(d, true, w, bias, y), ws, ws_packed, (hipStream_t)stream);
+    return fwd_common(d, true, w, bias, y, nullptr, ws, ws_packed, (hipStream_t)stream);
 }
+// the items of the data-gradient plan whose members' gradients are wanted, each on its own panel of ws (cacheable)
 static int dgrad_common(const m1_conv_desc_t* d, bool T, const float* w, const void* dy, void* const* dx, const int* accumulate,
                         void* ws, int ws_packed, hipStream_t st) {
-    if (dgrad_fused_ok(d) && !g_force_direct) {
-        GatherSpec gf = dgrad_fused_spec(d, T, w, dy, dx, accumulate);
-        if (m1_mfma_supported(gf)) {
-            bool any = false;
-            for (int i = 0; i < d->nsrc; ++i) any |= dx[i] != nullptr;
-            return any ? run_gather(gf, ws, ws_packed, st) : M1_OK;
-        }
-    }
-    int off = 0; size_t woff = 0;                         // member i's panel lives at its own offset of ws (cacheable)
-    for (int i = 0; i < d->nsrc; ++i) {
-        GatherSpec g = dgrad_spec(d, T, w, dy, dx[i], i, off);
-        g.accumulate = accumulate && accumulate[i] ? 1 : 0;
-        if (dx[i]) {
-            int rc = run_gather(g, ws ? (unsigned char*)ws + woff : nullptr, ws_packed, st); if (rc) return rc;
-        }
-        woff += gather_ws_bytes(g);
-        off += d->src[i].C;
+    const GatherPlan p = plan_gather(d, T, 1);
+    for (int k = 0; k < p.n; ++k) {
+        const GatherItem& it = p.item[k];
+        bool any = false;
+        for (int i = it.first; i < it.first + it.count; ++i) any |= dx[i] != nullptr;
+        if (!any) continue;
+        int rc = run_gather(dgrad_item_spec(d, p, k, w, dy, dx, accumulate), at(ws, it.off), ws_packed, st); if (rc) return rc;
     }
     return M1_OK;
 }
@@ -538,7 +509,7 @@ extern "C" int m1_conv3d_dgrad_inbwd(const m1_conv_desc_t* d, const float* w, co
     M1ProfScope ps(prof_name("conv3d_dgrad", d).s, 2.0 * conv_macs(d, false), conv_bytes(d, false), (hipStream_t)stream);
     *nparts = 0;
     if (g_force_direct) { void* dxs[1] = {da}; int acc0[1] = {0}; return dgrad_common(d, false, w, dy, dxs, acc0, ws, ws_packed, (hipStream_t)stream); }
-    GatherSpec g = dgrad_spec(d, false, w, dy, da, 0, 0);
+    GatherSpec g = dgrad_spec(d, false, w, dy, da, 0, 0);      // (one member: the only item of its plan, panel at offset 0)
     g.ib_x = x; g.ib_stats = stats; g.ib_gamma = gamma; g.ib_beta = beta; g.ib_slope = slope; g.ib_partial = partial; g.ib_nparts = nparts; g.ib_cap = partial_rows;
     return run_gather(g, ws, ws_packed, (hipStream_t)stream);
 }
@@ -551,7 +522,27 @@ extern "C" int m1_convT3d_dgrad(const m1_conv_desc_t* d, const float* w, const v
 }
 
 // ---- weight gradients ------------------------------------------------------------------------------------------
-#include <stdlib.h>
+// The weight gradient of concat member i, whose channels start at `off` of the concat, inside the whole gradient dw; db: the bias
+// gradient rides along (Conv3D only); rx: this member's partial-copy region.  The padded stem is member 0 of a copy of the
+// descriptor whose only member is the padded input.
+static WgradSpec wgrad_spec(const m1_conv_desc_t* d, bool T, const Geo& q, int i, int off, const void* dy, float* dw, float* db, float* rx,
+                            long long rx_floats) {
+    WgradSpec g{};
+    g.N = d->N; g.R = dw; g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
+    g.pd = q.pd; g.ph = q.ph; g.pw = q.pw; g.dtype = d->dtype;
+    g.rx = rx; g.rx_floats = rx_floats;
+    if (!T) {   // dw[tap][ci][co] = sum X[v*s+tap-p][ci] * dY[v][co]
+        g.A = d->src[i].ptr; g.CA = d->src[i].C; g.AD = d->D; g.AH = d->H; g.AW = d->W;
+        g.B = dy; g.CB = d->Cout; g.BD = q.OD; g.BH = q.OH; g.BW = q.OW;
+        g.RT = (long long)d->Cin * d->Cout; g.RSA = d->Cout; g.a_off = off; g.b_off = 0;
+        if (db) { g.bsum = db; g.bsum_tap = (q.pd * d->kh + q.ph) * d->kw + q.pw; }
+    } else {    // dw[tap][co][ci] = sum dOut[i*s+tap-pb][co] * In[i][ci]
+        g.A = dy; g.CA = d->Cout; g.AD = q.OD; g.AH = q.OH; g.AW = q.OW;
+        g.B = d->src[i].ptr; g.CB = d->src[i].C; g.BD = d->D; g.BH = d->H; g.BW = d->W;
+        g.RT = (long long)d->Cout * d->Cin; g.RSA = d->Cin; g.a_off = 0; g.b_off = off;
+    }
+    return g;
+}
 static bool tf_wanted(const WgradSpec& g) {
     int maxc = M1_CFG("M1_TF_MAXC", 128);
     // 32x32 channel tiles re-read dY once per 32 input channels and X once per 32 output channels: a win while the OUTPUT side
@@ -559,15 +550,52 @@ static bool tf_wanted(const WgradSpec& g) {
     if (g.CA > 64 && g.CB > 32) return false;
     return g.CA <= maxc && g.CB <= maxc && m1_tf_wgrad_supported(g);
 }
-static bool m1_tf_wgrad_supported_stem(const m1_conv_desc_t* d, const Geo& q) {
-    WgradSpec g{};
-    const int CP = d->dtype == M1_BF16 ? 8 : 4;
-    g.N = d->N; g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
-    g.pd = q.pd; g.ph = q.ph; g.pw = q.pw; g.dtype = d->dtype;
-    g.CA = CP; g.AD = d->D; g.AH = d->H; g.AW = d->W; g.CB = d->Cout; g.BD = q.OD; g.BH = q.OH; g.BW = q.OW;
-    g.RT = (long long)CP * d->Cout; g.RSA = d->Cout;
-    return d->dtype == M1_BF16 ? m1_tf_wgrad_supported(g) : m1_t3s_wgrad_supported(g);
+// What a rung of the ladder sees besides the member's spec.  run: the members from this one on that have its channel count (a
+// transposed conv has its members on the dY-less side: always 1), with their tensors and channel offsets for the kernels that
+// take such a run in ONE launch.
+struct WgCall {
+    bool T; int run; const void* Am[M1_MAX_SRC]; int aoffs[M1_MAX_SRC];
+    long long nw; int nbias; long long rx_floats; hipStream_t st;
+    const char** took;         // for M1_WG_LOG: the rung's name, unless the rung names the kernel it chose
+};
+static int equal_run(const m1_conv_desc_t* d, int i) {
+    int n = 1;
+    while (i + n < d->nsrc && d->src[i + n].C == d->src[i].C) ++n;
+    return n;
 }
+// THE order in which the weight-gradient kernels are tried for a member (wgrad_common walks it).  A rung whose gate holds runs; it
+// may still decline (M1_ERR_UNSUPPORTED / M1_ERR_WORKSPACE: nothing launched), then the next one is asked.  whole_run: the rung
+// consumes c.run members, else one.  m1_set_force_direct leaves only the rungs marked `forced`.
+struct WgRung {
+    const char* name; bool whole_run, forced;
+    bool (*gate)(const WgradSpec& g, const WgCall& c);
+    int (*run)(const WgradSpec& g, const WgCall& c);
+};
+static const WgRung WG_LADDER[] = {
+    // >= 64 channels on both sides: the 64x64-tile tap-fused kernel on 32x32x16 MFMAs, one launch for a run of equal-width
+    // members (dY staged once per kd slice for all of them, wgrad_t3.hip)
+    {"t3", true, false, [](const WgradSpec& g, const WgCall&) { return g.rx && m1_t3_wgrad_supported(g); },
+     [](const WgradSpec& g, const WgCall& c) { return m1_t3_wgrad(g, c.nw, c.nbias, c.st, c.run, c.Am, c.aoffs, c.rx_floats); }},
+    {"pwf", false, false, [](const WgradSpec& g, const WgCall& c) { return g.rx && g.dtype == M1_F32 && !c.T && m1_pwf_wgrad_supported(g); },
+     [](const WgradSpec& g, const WgCall& c) { return m1_pwf_wgrad(g, c.nw, c.nbias, c.st); }},
+    // fp32 layers the 64x64-tile kernel does not take (few channels on a side): the 32x32-tile tap-fused fp32 kernel
+    {"t3s", false, false, [](const WgradSpec& g, const WgCall&) { return g.rx && g.dtype == M1_F32 && m1_t3s_wgrad_supported(g); },
+     [](const WgradSpec& g, const WgCall& c) { return m1_t3s_wgrad(g, c.nw, c.nbias, c.st); }},
+    // a run of members with the same channel count on the tap-fused kernel: ONE launch (blockIdx.z = member)
+    {"tf-multi", true, false,
+     [](const WgradSpec& g, const WgCall& c) { int multi = M1_CFG("M1_TF_MULTI", 1); return multi && !c.T && g.rx && tf_wanted(g) && c.run > 1; },
+     [](const WgradSpec& g, const WgCall& c) { return m1_tf_wgrad_multi(g, c.nw, c.nbias, c.st, c.run, c.Am, c.aoffs, c.rx_floats); }},
+    {"tf", false, false, [](const WgradSpec& g, const WgCall&) { return tf_wanted(g); },
+     [](const WgradSpec& g, const WgCall& c) { return m1_tf_wgrad(g, c.nw, c.nbias, c.st); }},
+    // the terminal choice: whatever it answers is the member's result
+    {"terminal", false, true, [](const WgradSpec&, const WgCall&) { return true; },
+     [](const WgradSpec& g, const WgCall& c) {
+         if (g_force_direct == 2 && m1_skinny_wgrad_supported(g)) { *c.took = "skinny"; return m1_skinny_wgrad(g, c.st); }   // test hook for that kernel
+         if (!g_force_direct && m1_tap_wgrad_supported(g)) { *c.took = "tap"; return m1_tap_wgrad(g, c.nw, c.nbias, c.st); }
+         if (!g_force_direct && m1_mfma_wgrad_supported(g)) { *c.took = "mfma"; return m1_mfma_wgrad_ex(g, c.nw, c.nbias, c.st); }
+         *c.took = "direct"; return m1_direct_wgrad(g, c.st);
+     }},
+};
 static int wgrad_common(const m1_conv_desc_t* d, bool T, const void* dy, float* dw, float* db, void* ws, hipStream_t st,
                         int accumulate) {
     Geo q = T ? convT_geo(d) : conv_geo(d);
@@ -577,115 +605,54 @@ static int wgrad_common(const m1_conv_desc_t* d, bool T, const void* dy, float* 
     // transposed conv (its dOut is the SHIFTED operand) and the direct path keep the separate column-sum pass
     const bool fuse_db = db && !T && !g_force_direct;
     if (fuse_db && !accumulate && m1_zero_async(db, (size_t)d->Cout * sizeof(float), st) != M1_OK) return M1_ERR_LAUNCH;
-    int off = 0;
     const int nbias = fuse_db ? d->Cout : 0;
-    float* rx = nullptr; long long rx_floats = 0;              // partial-copy scratch: the tail of the caller's workspace
-    if (ws && wgrad_rx_bytes(d)) {
-        rx = reinterpret_cast<float*>((unsigned char*)ws + align256(m1_reduce_ws_floats(d->N, (long long)q.OD * q.OH * q.OW, d->Cout, 1) * sizeof(float)) +
-                                      256 + stem_ws_bytes(d, T));
-        rx_floats = (long long)(wgrad_rx_bytes(d) / sizeof(float));
-    }
-    if (stem_wanted(d, T) && ws && m1_tf_wgrad_supported_stem(d, q)) {
-        const int taps = d->kd * d->kh * d->kw, Cin = d->Cin;
-        const long long nvox = (long long)d->N * d->D * d->H * d->W;
-        unsigned char* base = (unsigned char*)ws + align256(m1_reduce_ws_floats(d->N, (long long)q.OD * q.OH * q.OW, d->Cout, 1) * sizeof(float)) + 256;
+    const WgradWs L = wgrad_ws(d, T);
+    float* const rx = reinterpret_cast<float*>(at(ws, L.rx));        // partial-copy scratch: the tail of the caller's workspace
+    const long long rx_floats = ws ? L.rx_floats : 0;
+    if (stem_wanted(d, T) && ws) {
         const bool f32 = d->dtype == M1_F32;
         const int CP = f32 ? 4 : 8;                       // padded channels: one 16-byte segment per voxel
-        uint4* x8 = reinterpret_cast<uint4*>(base);
-        float* r8 = reinterpret_cast<float*>(base + align256((size_t)nvox * 16));
-        const size_t nw8 = (size_t)taps * CP * d->Cout;
-        if (m1_zero_async(r8, nw8 * sizeof(float), st) != M1_OK) return M1_ERR_LAUNCH;
-        long long pb = (nvox + 255) / 256; if (pb > 8192) pb = 8192;
-        if (f32) hipLaunchKernelGGL(stem_pad4f_kernel, dim3((unsigned)pb), dim3(256), 0, st, (const float*)d->src[0].ptr, reinterpret_cast<float4*>(x8), nvox, Cin);
-        else hipLaunchKernelGGL(stem_pad8_kernel, dim3((unsigned)pb), dim3(256), 0, st, (const unsigned short*)d->src[0].ptr, x8, nvox, Cin);
-        WgradSpec g{};
-        g.N = d->N; g.R = r8; g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
-        g.pd = q.pd; g.ph = q.ph; g.pw = q.pw; g.dtype = d->dtype;
-        g.A = x8; g.CA = CP; g.AD = d->D; g.AH = d->H; g.AW = d->W;
-        g.B = dy; g.CB = d->Cout; g.BD = q.OD; g.BH = q.OH; g.BW = q.OW;
-        g.RT = (long long)CP * d->Cout; g.RSA = d->Cout; g.a_off = 0; g.b_off = 0;
-        g.rx = rx; g.rx_floats = rx_floats;
-        if (fuse_db) { g.bsum = db; g.bsum_tap = (q.pd * d->kh + q.ph) * d->kw + q.pw; }
-        const int was = m1_fold_defer_set(0);          // (stem_fold_kernel below reads the folded 8-channel gradient)
-        int rc = f32 ? m1_t3s_wgrad(g, (long long)nw8, nbias, st) : m1_tf_wgrad(g, (long long)nw8, nbias, st);
-        m1_fold_defer_set(was);
-        if (rc == M1_OK) {
-            hipLaunchKernelGGL(stem_fold_kernel, dim3((taps * Cin * d->Cout + 255) / 256), dim3(256), 0, st, r8, dw, taps, Cin, d->Cout, CP);
-            return m1_check_launch();
-        }
-        if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) return rc;      // declined: nothing launched, take the generic path
-    }
-    for (int i = 0; i < d->nsrc; ++i) {
-        WgradSpec g{};
-        g.N = d->N; g.R = dw; g.kd = d->kd; g.kh = d->kh; g.kw = d->kw; g.sd = d->sd; g.sh = d->sh; g.sw = d->sw;
-        g.pd = q.pd; g.ph = q.ph; g.pw = q.pw; g.dtype = d->dtype;
-        g.rx = rx ? rx + (long long)i * rx_floats : nullptr; g.rx_floats = rx_floats;          // this member's own copy region
-        if (!T) {   // dw[tap][ci][co] = sum X[v*s+tap-p][ci] * dY[v][co]
-            g.A = d->src[i].ptr; g.CA = d->src[i].C; g.AD = d->D; g.AH = d->H; g.AW = d->W;
-            g.B = dy; g.CB = d->Cout; g.BD = q.OD; g.BH = q.OH; g.BW = q.OW;
-            g.RT = (long long)d->Cin * d->Cout; g.RSA = d->Cout; g.a_off = off; g.b_off = 0;
-            if (fuse_db && i == 0) { g.bsum = db; g.bsum_tap = (q.pd * d->kh + q.ph) * d->kw + q.pw; }
-        } else {    // dw[tap][co][ci] = sum dOut[i*s+tap-pb][co] * In[i][ci]
-            g.A = dy; g.CA = d->Cout; g.AD = q.OD; g.AH = q.OH; g.AW = q.OW;
-            g.B = d->src[i].ptr; g.CB = d->src[i].C; g.BD = d->D; g.BH = d->H; g.BW = d->W;
-            g.RT = (long long)d->Cout * d->Cin; g.RSA = d->Cin; g.a_off = 0; g.b_off = off;
-        }
-        int rc = M1_ERR_UNSUPPORTED;
-        int wlog = M1_CFG("M1_WG_LOG", 0);
-        // >= 64 channels on both sides, stride 1: the 64x64-tile tap-fused kernel on 32x32x16 MFMAs, one launch for a run of
-        // equal-width members (dY staged once per kd slice for all of them, wgrad_t3.hip)
-        if (!g_force_direct && rx && m1_t3_wgrad_supported(g)) {
-            int n = 1;                                    // (transposed conv: the members are on the dY-less side, one call each)
-            while (!T && i + n < d->nsrc && d->src[i + n].C == d->src[i].C) ++n;
-            const void* Am[M1_MAX_SRC]; int aoffs[M1_MAX_SRC]; int o = off;
-            for (int m = 0; m < n; ++m) { Am[m] = d->src[i + m].ptr; aoffs[m] = o; o += d->src[i + m].C; }
-            rc = m1_t3_wgrad(g, (long long)nw, nbias, st, n, Am, aoffs, rx_floats);
-            if (wlog) fprintf(stderr, "wgrad %s N%d B %dx%dx%d CA %d x%d CB %d k%d%d%d s%d%d%d -> t3 rc %d\n", T ? "convT" : "conv", g.N, g.BD, g.BH, g.BW, g.CA, n, g.CB, g.kd, g.kh, g.kw, g.sd, g.sh, g.sw, rc);
-            if (rc == M1_OK) { off = o; i += n - 1; continue; }
-            if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) return rc;
-            rc = M1_ERR_UNSUPPORTED;
-        }
-        if (!g_force_direct && rx && g.dtype == M1_F32 && !T && m1_pwf_wgrad_supported(g)) {
-            rc = m1_pwf_wgrad(g, (long long)nw, nbias, st);
-            if (wlog) fprintf(stderr, "wgrad conv N%d B %dx%dx%d CA %d CB %d k111 -> pwf rc %d\n", g.N, g.BD, g.BH, g.BW, g.CA, g.CB, rc);
-            if (rc == M1_OK) { off += d->src[i].C; continue; }
-            if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) return rc;
-            rc = M1_ERR_UNSUPPORTED;
-        }
-        // fp32 layers the 64x64-tile kernel does not take (few channels on a side): the 32x32-tile tap-fused fp32 kernel
-        if (!g_force_direct && rx && g.dtype == M1_F32 && m1_t3s_wgrad_supported(g)) {
-            rc = m1_t3s_wgrad(g, (long long)nw, nbias, st);
-            if (wlog) fprintf(stderr, "wgrad %s N%d B %dx%dx%d CA %d CB %d k%d%d%d s%d%d%d -> t3s rc %d\n", T ? "convT" : "conv", g.N, g.BD, g.BH, g.BW, g.CA, g.CB, g.kd, g.kh, g.kw, g.sd, g.sh, g.sw, rc);
-            if (rc == M1_OK) { off += d->src[i].C; continue; }
-            if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) return rc;
-            rc = M1_ERR_UNSUPPORTED;
-        }
-        // a run of members with the same channel count on the tap-fused kernel: ONE launch (blockIdx.z = member)
-        int multi = M1_CFG("M1_TF_MULTI", 1);
-        if (multi && !T && !g_force_direct && rx && tf_wanted(g)) {
-            int n = 1;
-            while (i + n < d->nsrc && d->src[i + n].C == d->src[i].C) ++n;
-            if (n > 1) {
-                const void* Am[M1_MAX_SRC]; int aoffs[M1_MAX_SRC]; int o = off;
-                for (int m = 0; m < n; ++m) { Am[m] = d->src[i + m].ptr; aoffs[m] = o; o += d->src[i + m].C; }
-                rc = m1_tf_wgrad_multi(g, (long long)nw, nbias, st, n, Am, aoffs, rx_floats);
-                if (wlog) fprintf(stderr, "wgrad conv N%d B %dx%dx%d CA %d x%d CB %d -> tap-fused multi rc %d\n", g.N, g.BD, g.BH, g.BW, g.CA, n, g.CB, rc);
-                if (rc == M1_OK) { off = o; i += n - 1; continue; }
-                if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) return rc;
-                rc = M1_ERR_UNSUPPORTED;
+        uint4* x8 = reinterpret_cast<uint4*>(at(ws, L.x8));
+        float* r8 = reinterpret_cast<float*>(at(ws, L.r8));
+        m1_conv_desc_t dp = *d; dp.Cin = CP; dp.src[0].ptr = x8; dp.src[0].C = CP;       // the padded member, its gradient in r8
+        const WgradSpec g = wgrad_spec(&dp, false, q, 0, 0, dy, r8, fuse_db ? db : nullptr, rx, rx_floats);
+        if (f32 ? m1_t3s_wgrad_supported(g) : m1_tf_wgrad_supported(g)) {
+            const int taps = d->kd * d->kh * d->kw, Cin = d->Cin;
+            const long long nvox = (long long)d->N * d->D * d->H * d->W;
+            const size_t nw8 = (size_t)taps * CP * d->Cout;
+            if (m1_zero_async(r8, nw8 * sizeof(float), st) != M1_OK) return M1_ERR_LAUNCH;
+            long long pb = (nvox + 255) / 256; if (pb > 8192) pb = 8192;
+            if (f32) hipLaunchKernelGGL(stem_pad4f_kernel, dim3((unsigned)pb), dim3(256), 0, st, (const float*)d->src[0].ptr, reinterpret_cast<float4*>(x8), nvox, Cin);
+            else hipLaunchKernelGGL(stem_pad8_kernel, dim3((unsigned)pb), dim3(256), 0, st, (const unsigned short*)d->src[0].ptr, x8, nvox, Cin);
+            const int was = m1_fold_defer_set(0);      // (stem_fold_kernel below reads the folded 8-channel gradient)
+            int rc = f32 ? m1_t3s_wgrad(g, (long long)nw8, nbias, st) : m1_tf_wgrad(g, (long long)nw8, nbias, st);
+            m1_fold_defer_set(was);
+            if (rc == M1_OK) {
+                hipLaunchKernelGGL(stem_fold_kernel, dim3((taps * Cin * d->Cout + 255) / 256), dim3(256), 0, st, r8, dw, taps, Cin, d->Cout, CP);
+                return m1_check_launch();
             }
+            if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) return rc;      // declined: nothing launched, take the generic path
         }
-        if (!g_force_direct && tf_wanted(g)) rc = m1_tf_wgrad(g, (long long)nw, nbias, st);   // may decline (no launch)
-        if (wlog) fprintf(stderr, "wgrad %s N%d B %dx%dx%d CA %d CB %d k%d%d%d s%d%d%d -> %s\n", T ? "convT" : "conv", g.N, g.BD, g.BH, g.BW, g.CA, g.CB,
-                          g.kd, g.kh, g.kw, g.sd, g.sh, g.sw, rc == M1_OK ? "tap-fused" : (m1_tap_wgrad_supported(g) ? "tap" : "mfma"));
-        if (rc == M1_OK) { off += d->src[i].C; continue; }
-        if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) return rc;
-        if (g_force_direct == 2 && m1_skinny_wgrad_supported(g)) rc = m1_skinny_wgrad(g, st);   // test hook for that kernel
-        else if (!g_force_direct && m1_tap_wgrad_supported(g)) rc = m1_tap_wgrad(g, (long long)nw, nbias, st);
-        else if (!g_force_direct && m1_mfma_wgrad_supported(g)) rc = m1_mfma_wgrad_ex(g, (long long)nw, nbias, st);
-        else rc = m1_direct_wgrad(g, st);
+    }
+    const int wlog = M1_CFG("M1_WG_LOG", 0);
+    for (int i = 0, off = 0; i < d->nsrc;) {
+        WgCall c{};
+        c.T = T; c.nw = (long long)nw; c.nbias = nbias; c.rx_floats = rx_floats; c.st = st;
+        c.run = T ? 1 : equal_run(d, i);
+        for (int m = 0, o = off; m < c.run; ++m) { c.Am[m] = d->src[i + m].ptr; c.aoffs[m] = o; o += d->src[i + m].C; }
+        const WgradSpec g = wgrad_spec(d, T, q, i, off, dy, dw, fuse_db && i == 0 ? db : nullptr, rx ? rx + (long long)i * rx_floats : nullptr,
+                                       rx_floats);
+        int rc = M1_ERR_UNSUPPORTED, used = 1;
+        for (const WgRung& r : WG_LADDER) {
+            if ((g_force_direct && !r.forced) || !r.gate(g, c)) continue;
+            const char* took = r.name; c.took = &took;
+            rc = r.run(g, c); used = r.whole_run ? c.run : 1;
+            if (wlog) fprintf(stderr, "wgrad %s N%d B %dx%dx%d CA %d x%d CB %d k%d%d%d s%d%d%d -> %s rc %d\n", T ? "convT" : "conv", g.N, g.BD,
+                              g.BH, g.BW, g.CA, used, g.CB, g.kd, g.kh, g.kw, g.sd, g.sh, g.sw, took, rc);
+            if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) break;      // taken or a hard error; else declined: the next rung
+        }
         if (rc) return rc;
-        off += d->src[i].C;
+        for (int m = 0; m < used; ++m) off += d->src[i++].C;
     }
     if (db && !fuse_db) {
         if (!ws) return M1_ERR_WORKSPACE;
