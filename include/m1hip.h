@@ -682,6 +682,36 @@ int m1_adam_amsgrad(float* p, const float* g, float* m, float* v, float* vhat, l
 /* step_dev[0] += 1 (may be NULL); rng_dev[1] += 1 (may be NULL). */
 int m1_step_advance(int* step_dev, uint64_t* rng_dev, void* stream);
 
+/* ---- Guarded step: tf.keras' clipvalue / global_clipnorm and a skip of non-finite gradients, decided on the device ----
+ * All of it works on the regularised gradient gr = g*grad_scale + 2*lambda*p of m1_adam_amsgrad (same ranges, same fp32 evaluation):
+ * Keras clips what the optimiser receives.  clipvalue clamps every gr to [-clipvalue, clipvalue] first (NaN stays NaN, +-Inf is
+ * clamped); the global norm is taken over the clamped values.  0 switches clipvalue / global_clipnorm off; negative, NaN and Inf
+ * are M1_ERR_BAD_ARG.  The 16-byte record (device memory, 16-byte aligned, zero before its first use) carries the decision from
+ * m1_grad_norm to m1_adam_amsgrad_ctl and m1_step_advance_ctl inside one captured step. */
+typedef struct {
+    float norm;        /* (float)sqrt(sum of clamp(gr)^2), the sum in fp64: Inf / NaN when a gradient is */
+    float coef;        /* global_clipnorm / norm when global_clipnorm > 0 and norm > global_clipnorm, otherwise exactly 1;
+                        * NaN when the sum is not finite, global_clipnorm > 0 and the guard is off (as tf.clip_by_global_norm) */
+    int32_t apply;     /* 0: skip_nonfinite is on and the sum is not finite -- the update and the step advance do nothing */
+    int32_t skipped;   /* number of launches of m1_grad_norm on this record that set apply = 0 */
+} m1_step_ctl_t;
+/* Bytes of `ws` for n elements (pure host call; 8-byte aligned workspace, no initialisation needed). */
+size_t m1_grad_norm_ws(long long n);
+/* Two launches: per-block fp64 partial sums into ws (grid = f(n, M1_EW_BLOCKS) <= 2048 blocks; no atomics: the same input gives the
+ * same bits), then one block that folds them in a fixed order and writes *ctl.  p is read only when l2_kernel or l2_bias is
+ * non-zero (it must still be a valid 16-byte aligned pointer).  g, p 16-byte aligned. */
+int m1_grad_norm(const float* g, const float* p, long long n, long long n_kernel, long long n_bias, float l2_kernel,
+                 float l2_bias, float grad_scale, float clipvalue, float global_clipnorm, int skip_nonfinite, void* ws,
+                 size_t ws_bytes, m1_step_ctl_t* ctl, void* stream);
+/* m1_adam_amsgrad on clamp(gr, clipvalue) * ctl->coef; nothing is read or written when ctl->apply == 0.  With clipvalue == 0 and
+ * coef == 1 the result equals m1_adam_amsgrad's bit for bit. */
+int m1_adam_amsgrad_ctl(float* p, const float* g, float* m, float* v, float* vhat, long long n, long long n_kernel,
+                        long long n_bias, float l2_kernel, float l2_bias, float grad_scale, const float* lr_dev,
+                        float beta1, float beta2, float eps, const int* step_dev, float clipvalue,
+                        const m1_step_ctl_t* ctl, void* stream);
+/* step_dev[0] += ctl->apply. */
+int m1_step_advance_ctl(int* step_dev, const m1_step_ctl_t* ctl, void* stream);
+
 /* Deferred folds of the weight-gradient partial copies (no reference counterpart; the reference's tf.GradientTape sums weight
  * gradients inside each op).  m1_conv3d_wgrad / m1_convT3d_wgrad split the voxels over blocks, every block stores its partial
  * tile into a copy inside `ws`, and a fold kernel adds the copies into dw / db in a fixed order.  After m1_wgrad_defer(1) the

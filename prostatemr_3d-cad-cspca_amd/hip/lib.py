@@ -223,6 +223,10 @@ SIGNATURES = {
     "m1_cast": (_i, [_vp, _i, _vp, _i, _ll, _vp]),
     "m1_adam_amsgrad": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _vp]),
     "m1_step_advance": (_i, [_vp, _vp, _vp]),
+    "m1_grad_norm_ws": (_sz, [_ll]),
+    "m1_grad_norm": (_i, [_vp, _vp, _ll, _ll, _ll, _f, _f, _f, _f, _f, _i, _vp, _sz, _vp, _vp]),
+    "m1_adam_amsgrad_ctl": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _f, _vp, _vp]),
+    "m1_step_advance_ctl": (_i, [_vp, _vp, _vp]),
     "m1_wgrad_defer": (_i, [_i]),
     "m1_wgrad_fold_pending": (_i, [_vp]),
     "m1_wgrad_fold_drop": (_i, []),

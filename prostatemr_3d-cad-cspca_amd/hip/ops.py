@@ -1559,6 +1559,48 @@ def step_advance(step_dev, rng_dev):
     L.check(L.load().m1_step_advance(_p(step_dev), _p(rng_dev), _stream()), "m1_step_advance")
 
 
+# ---- guarded optimiser step (csrc/optim.hip): clipvalue / global_clipnorm / non-finite skip through a 16-byte device record ----
+def grad_norm_ws(n: int) -> int:
+    """Bytes of the workspace ``grad_norm_`` needs for n elements (host only)."""
+    return int(L.load().m1_grad_norm_ws(int(n)))
+
+
+def new_step_ctl(device) -> torch.Tensor:
+    """A zeroed control record m1_step_ctl_t {float norm; float coef; int apply; int skipped} as four int32 words."""
+    return torch.zeros(4, dtype=torch.int32, device=device)
+
+
+def read_step_ctl(ctl: torch.Tensor) -> dict:
+    """The record on the host (synchronises)."""
+    w = ctl.cpu()
+    f = w.view(torch.float32)
+    return {"norm": float(f[0]), "coef": float(f[1]), "apply": int(w[2]), "skipped": int(w[3])}
+
+
+def grad_norm_(g, p, n_kernel, n_bias, l2_kernel, l2_bias, grad_scale, clipvalue, global_clipnorm, skip_nonfinite, ws, ctl):
+    """Norm pass + control pass: ``ctl`` receives the global norm of the (clamped) regularised gradient, the clip coefficient and the
+    apply / skip decision.  0 switches clipvalue / global_clipnorm off.  ``ws``: at least grad_norm_ws(g.numel()) bytes."""
+    _req(g, p, ws, ctl)
+    L.check(L.load().m1_grad_norm(_p(g), _p(p), g.numel(), int(n_kernel), int(n_bias), float(l2_kernel), float(l2_bias),
+                                  float(grad_scale), float(clipvalue), float(global_clipnorm), int(bool(skip_nonfinite)), _p(ws),
+                                  ws.numel() * ws.element_size(), _p(ctl), _stream()), "m1_grad_norm")
+
+
+def adam_amsgrad_ctl_(p, g, m, v, vhat, n_kernel, n_bias, l2_kernel, l2_bias, grad_scale, lr_dev, beta1, beta2, eps, step_dev,
+                      clipvalue, ctl):
+    """adam_amsgrad_ on clamp(gr, clipvalue) * ctl.coef; a no-op when ctl.apply == 0."""
+    _req(p, g, m, v, vhat, lr_dev, step_dev, ctl)
+    L.check(L.load().m1_adam_amsgrad_ctl(_p(p), _p(g), _p(m), _p(v), _p(vhat), p.numel(), int(n_kernel), int(n_bias),
+                                         float(l2_kernel), float(l2_bias), float(grad_scale), _p(lr_dev), float(beta1), float(beta2),
+                                         float(eps), _p(step_dev), float(clipvalue), _p(ctl), _stream()), "m1_adam_amsgrad_ctl")
+
+
+def step_advance_ctl(step_dev, ctl):
+    """step_dev += ctl.apply."""
+    _req(step_dev, ctl)
+    L.check(L.load().m1_step_advance_ctl(_p(step_dev), _p(ctl), _stream()), "m1_step_advance_ctl")
+
+
 def set_force_direct(on: bool):
     """Test hook: route every conv through the generic direct kernels instead of the matrix-core kernels."""
     _FORCE_DIRECT[0] = bool(on)

@@ -123,12 +123,39 @@ class Adam:
     """tf.keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon=1e-7, amsgrad=True).
 
     ``w -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(vhat)+eps)`` with ``vhat = max(vhat, v)`` -- epsilon OUTSIDE the
-    bias-corrected sqrt, unlike torch.optim.Adam.  Only amsgrad=True (the reference's setting) is implemented."""
+    bias-corrected sqrt, unlike torch.optim.Adam.  Only amsgrad=True (the reference's setting) is implemented.
+
+    The guarded step (off by default; with all three arguments at their defaults the optimiser makes exactly the calls it made without
+    them).  It works on the regularised gradient ``g*grad_scale + 2*lambda*w`` the update itself consumes -- Keras clips what the
+    optimiser receives, and the fused L2 term is part of it -- and decides on the device, inside a captured step, after the gradient
+    exchange (every rank sees the same all-reduced buffer and decides alike):
+
+    * ``clipvalue``: every gradient element is clamped to [-clipvalue, clipvalue] (tf.keras' ``clipvalue``); an Inf is clamped too.
+    * ``global_clipnorm``: when the L2 norm over ALL (clamped) elements exceeds it, every element is scaled by
+      ``global_clipnorm / norm`` (tf.keras' ``global_clipnorm``, tf.clip_by_global_norm).
+    * ``skip_nonfinite`` (no Keras counterpart): a step whose gradient norm is NaN or Inf changes nothing -- weights, ``m``, ``v``,
+      ``vhat`` and Adam's own step counter ``t`` keep their bits -- and is counted in ``skipped_steps``.  ``iterations`` (the host
+      counter the learning-rate schedule reads) still advances on a skipped step: the schedule follows the batches seen, and the
+      host cannot know about the skip without a synchronisation.
+    * ``clipnorm`` (Keras' per-variable norm) is not built.
+
+    ``grad_norm`` / ``skipped_steps`` read the device record of the last step (they synchronise); ``step_ctl`` is the record itself
+    (int32[4]: float norm, float coef, int apply, int skipped) for callers inside a graph."""
     handles_l2 = True
 
-    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=True):
+    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=True, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None, skip_nonfinite=False):
         if not amsgrad:
             raise NotImplementedError("the reference trains with amsgrad=True (train_model.py:120); only that is built")
+        if clipnorm is not None:
+            raise NotImplementedError("clipnorm (the per-variable norm) is not built: use global_clipnorm (one norm over all variables)")
+        for name, val in (("clipvalue", clipvalue), ("global_clipnorm", global_clipnorm)):
+            if val is not None and not (float(val) > 0.0 and math.isfinite(float(val))):
+                raise ValueError(f"{name} must be a positive finite number or None, got {val!r}")
+        self.clipvalue = None if clipvalue is None else float(clipvalue)
+        self.global_clipnorm = None if global_clipnorm is None else float(global_clipnorm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.step_ctl: Optional[torch.Tensor] = None
         self.learning_rate = learning_rate
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
         self.flatp: Optional[FlatParams] = None
@@ -160,7 +187,32 @@ class Adam:
         self.step_dev = torch.ones(1, dtype=torch.int32, device=dev)
         self.l2_kernel = float(getattr(model, "l2_kernel", 0.0))
         self.l2_bias = float(getattr(model, "l2_bias", 0.0))
+        if self.guarded:
+            self._norm_ws = torch.empty(max(ops.grad_norm_ws(self.flatp.flat.numel()), 8), dtype=torch.uint8, device=dev)
+            self.step_ctl = ops.new_step_ctl(dev)
         return self
+
+    @property
+    def guarded(self) -> bool:
+        """True when any of clipvalue / global_clipnorm / skip_nonfinite is on: apply_flat then takes the guarded path."""
+        return self.clipvalue is not None or self.global_clipnorm is not None or self.skip_nonfinite
+
+    def _ctl(self) -> dict:
+        if not self.guarded:
+            raise RuntimeError("grad_norm / skipped_steps need clipvalue, global_clipnorm or skip_nonfinite: the plain step computes no norm")
+        if self.step_ctl is None:
+            raise RuntimeError("bind() the optimiser to a model first")
+        return ops.read_step_ctl(self.step_ctl)
+
+    @property
+    def grad_norm(self) -> float:
+        """Global L2 norm of the last step's regularised (and value-clamped) gradient, before the norm clip.  Synchronises."""
+        return self._ctl()["norm"]
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps skipped so far because their gradient norm was not finite.  Synchronises."""
+        return self._ctl()["skipped"]
 
     def zero_grad(self):
         for p in self.flatp.params:
@@ -218,9 +270,18 @@ class Adam:
     def apply_flat(self):
         """Fused update from the flat gradient buffer (already gathered / all-reduced)."""
         f = self.flatp
-        ops.adam_amsgrad_(f.flat, f.grad, self.m, self.v, self.vhat, f.n_kernel, f.n_bias, self.l2_kernel, self.l2_bias,
-                          self.grad_scale, self.lr_dev, self.beta_1, self.beta_2, self.epsilon, self.step_dev)
-        ops.step_advance(self.step_dev, None)
+        if self.guarded:
+            # norm + control -> controlled update -> conditional advance, all through the device record: nothing here looks at a value
+            cv, cn = self.clipvalue or 0.0, self.global_clipnorm or 0.0
+            ops.grad_norm_(f.grad, f.flat, f.n_kernel, f.n_bias, self.l2_kernel, self.l2_bias, self.grad_scale, cv, cn,
+                           self.skip_nonfinite, self._norm_ws, self.step_ctl)
+            ops.adam_amsgrad_ctl_(f.flat, f.grad, self.m, self.v, self.vhat, f.n_kernel, f.n_bias, self.l2_kernel, self.l2_bias,
+                                  self.grad_scale, self.lr_dev, self.beta_1, self.beta_2, self.epsilon, self.step_dev, cv, self.step_ctl)
+            ops.step_advance_ctl(self.step_dev, self.step_ctl)
+        else:
+            ops.adam_amsgrad_(f.flat, f.grad, self.m, self.v, self.vhat, f.n_kernel, f.n_bias, self.l2_kernel, self.l2_bias,
+                              self.grad_scale, self.lr_dev, self.beta_1, self.beta_2, self.epsilon, self.step_dev)
+            ops.step_advance(self.step_dev, None)
         ops.repack_all()                 # weights changed behind torch's back: refresh every cached weight panel (hip/panels.py)
 
     def step(self):

@@ -29,6 +29,11 @@ What differs from the reference, and why (its harness bugs a
     entropy of n draws with fresh dropout masks and latent samples, unets/networks.py), for a caller's own validation loop.
   * checkpoints are ``model_weights_NNN.npz`` (callbacks.py); the fold-finished test uses the intended file name
     (the reference formats a set literal into it, T:103).
+  * guarded optimiser step (flags of this build, all off by default; the reference passes none of them to its Adam, T:120):
+    ``--GRAD_CLIP_VALUE v`` and ``--GRAD_CLIP_NORM c`` are tf.keras' ``clipvalue`` / ``global_clipnorm`` (0 = off), applied to the
+    gradient with the L2 term in it; ``--SKIP_NONFINITE 1`` leaves weights and moments untouched on a step whose gradient norm is
+    NaN or Inf.  With any of them on, ``train_step``'s logs gain ``grad_norm`` and ``skipped`` (the running count; ``fit`` averages
+    every log over the epoch's steps, these two included; ``model.optimizer.skipped_steps`` is the exact count).
 """
 from __future__ import annotations
 
@@ -129,7 +134,20 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--IMAGE_SPATIAL_DIMS', type=int, default=[20, 160, 160], nargs=3, help="(D,H,W) of synthetic volumes")
     prsr.add_argument('--COMPUTE_DTYPE', type=str, default="bf16", choices=["bf16", "fp32"], help="activation storage type")
     prsr.add_argument('--SEED', type=int, default=0)
+    # This build's guarded optimiser step (optim.Adam): all off by default
+    prsr.add_argument('--GRAD_CLIP_NORM', type=float, default=0.0, help="tf.keras global_clipnorm over all variables, 0 = off")
+    prsr.add_argument('--GRAD_CLIP_VALUE', type=float, default=0.0, help="tf.keras clipvalue per gradient element, 0 = off")
+    prsr.add_argument('--SKIP_NONFINITE', type=int, default=0, help="1: a step whose gradient norm is NaN / Inf changes nothing")
     return prsr
+
+
+def optimizer_kwargs(args) -> dict:
+    """The guarded-step arguments of optim.Adam from the flags: 0 means off (None); a negative value is an error."""
+    for name in ("GRAD_CLIP_NORM", "GRAD_CLIP_VALUE"):
+        if getattr(args, name) < 0 or not math.isfinite(getattr(args, name)):
+            raise ValueError(f"--{name} must be a finite number >= 0 (0 = off), got {getattr(args, name)}")
+    return dict(global_clipnorm=args.GRAD_CLIP_NORM or None, clipvalue=args.GRAD_CLIP_VALUE or None,
+                skip_nonfinite=bool(args.SKIP_NONFINITE))
 
 
 # ---- data -----------------------------------------------------------------------------------------------------
@@ -251,7 +269,7 @@ def train_fold(args, f: int, device, rank: int = 0, world: int = 1):
     # Optimizer (T:120-121)
     if args.OPTIMIZER != 'adam':
         raise NotImplementedError("only --OPTIMIZER adam (Adam amsgrad, train_model.py:120) runs on the fused HIP optimiser")
-    OPTIMIZER_SET = optim.Adam(learning_rate=BASE_LR, amsgrad=True)
+    OPTIMIZER_SET = optim.Adam(learning_rate=BASE_LR, amsgrad=True, **optimizer_kwargs(args))
     # Losses (T:124-131)
     if args.LOSS_MODE == 'distribution_focal':
         if len(args.FOCAL_LOSS_ALPHA) != NUM_CLASSES:                           # T:154-155

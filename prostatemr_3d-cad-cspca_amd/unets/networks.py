@@ -1075,4 +1075,6 @@ class M1(LoadableModel):
         self.advance_rng()
         logs = {"loss": float((total + reg).detach())}
         logs.update({k: float(v.detach()) for k, v in parts.items()})
+        if getattr(opt, "guarded", False):          # (the loss above already synchronised)
+            logs["grad_norm"], logs["skipped"] = opt.grad_norm, opt.skipped_steps
         return logs
