@@ -712,6 +712,32 @@ int m1_adam_amsgrad_ctl(float* p, const float* g, float* m, float* v, float* vha
 /* step_dev[0] += ctl->apply. */
 int m1_step_advance_ctl(int* step_dev, const m1_step_ctl_t* ctl, void* stream);
 
+/* ---- Per-case scoring of a validation batch : callbacks.py:17-40 (dice_3d), losses.py:32-41 (Focal.FL) ----
+ * One streaming pass (csrc/validate.hip) over p (B, voxels, K) fp32 -- the softmax, or the mean of n draws --, y (B, voxels, K) one-hot
+ * (y_dtype: enum m1_val_dtype) and entropy (B, voxels) fp32 or NULL leaves one record of 40 doubles per case:
+ *   focal          sum over voxels and classes of alpha_c * y * (1 - q)^gamma * (y * -log q), q = clip(p_c / sum_k p_k, 1e-7, 1 - 1e-7)
+ *                  evaluated in fp32 as m1_focal_fwd evaluates it, summed in fp64: the mean over the batch is Focal.FL(y, p)
+ *   entropy_sum, entropy_fg_sum   over all voxels / over voxels whose true class (the argmax of y) is 1 or higher; 0 without entropy
+ *   n_voxels, n_fg                voxels of the case / of them with a true class of 1 or higher
+ *   cls[c].sum_p, sum_y, sum_py   fp64 sums of p_c, y_c and p_c * y_c: dice_3d = (2 sum_py + 1e-7) / (sum_p + sum_y + 1e-7)
+ *   cls[c].n_pred, n_true, n_both voxels whose argmax of p / of y / of both is c (the lowest index among equals, as np.argmax)
+ *   cls[c].p_max                  the largest p_c of the case (0 when every p_c is negative or NaN)
+ * Counts are whole numbers stored as doubles; unused slots, and the classes >= K, are 0.
+ * Two launches: per (block, case) one partial row of 40 doubles into ws, then one block per case that folds the rows in a fixed
+ * order.  No atomics, no memset / memcpy nodes; the grid is a function of (B, voxels, K) alone and pointer alignment only widens the
+ * loads, so a record repeats bit for bit.  alpha: K HOST floats.  ws: m1_val_score_ws bytes (pure host call), 8-byte aligned, no
+ * initialisation needed.  NULL p / y / alpha / records / ws, a pointer not aligned to its element (records, ws: 8 bytes), a y_dtype
+ * outside the enum, B, K or voxels <= 0: M1_ERR_BAD_ARG; K > 4 or B > 65535: M1_ERR_UNSUPPORTED; ws_bytes too small:
+ * M1_ERR_WORKSPACE; all before any launch. */
+enum m1_val_dtype { M1_VAL_Y_F32 = 0, M1_VAL_Y_U8 = 1 };
+typedef struct {
+    double focal, entropy_sum, entropy_fg_sum, n_voxels, n_fg, _head[3];
+    struct { double sum_p, sum_y, sum_py, n_pred, n_true, n_both, p_max, _pad; } cls[4];
+} m1_val_record_t; /* 320 bytes */
+size_t m1_val_score_ws(int B, long long voxels, int K);
+int m1_val_score(const float* p, const void* y, int y_dtype, const float* entropy, const float* alpha, float gamma, int B,
+                 long long voxels, int K, m1_val_record_t* records, void* ws, size_t ws_bytes, void* stream);
+
 /* Deferred folds of the weight-gradient partial copies (no reference counterpart; the reference's tf.GradientTape sums weight
  * gradients inside each op).  m1_conv3d_wgrad / m1_convT3d_wgrad split the voxels over blocks, every block stores its partial
  * tile into a copy inside `ws`, and a fold kernel adds the copies into dw / db in a fixed order.  After m1_wgrad_defer(1) the

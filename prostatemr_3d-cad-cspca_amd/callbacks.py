@@ -1,12 +1,12 @@
 """Train-time callbacks of the thin trainer, with the class surface of the reference's callbacks.py
 (tf2.5/scripts/callbacks.py): ``WeightsSaver`` (CB:44-75), ``ReduceLR_Schedule`` (CB:79-101), ``PolyLR_Schedule``
-(CB:105-119) and ``ResumeTraining`` (CB:195-215).  Keras-style hooks (``on_epoch_begin/on_epoch_end``) driven by
-``LoadableModel.fit``.
+(CB:105-119) and ``ResumeTraining`` (CB:195-215), and ``Validate``, this build's train-time validation (validation.py).
+Keras-style hooks (``on_epoch_begin/on_epoch_end``) driven by ``LoadableModel.fit``.
 
 Checkpoints are ``model_weights_NNN.npz`` (Keras tensor layouts under App. E names + the constructor config; h5py is not
 in the image) instead of ``model_weights_NNN.h5``.  The reference's harness bugs are not reproduced:
 ``ResumeTraining`` overwrites its own ``weights_dir`` argument (CB:196) -- here it scans the directory it was given;
-the FROC validation callbacks it imports do not exist in the reference and are out of scope.
+the FROC validation callbacks it imports ``compute_FROC`` for do not exist in the reference: ``Validate`` is this project's own.
 """
 from __future__ import annotations
 
@@ -65,6 +65,59 @@ class WeightsSaver(Callback):
                     old = weights_path(self.D, (self.epoch + 1) - self.N)
                     if os.path.exists(old):
                         os.remove(old)
+        self.epoch += 1
+
+
+class Validate(Callback):
+    """Validation every N epochs (the slot the reference leaves open, train_model.py:240-245): at the end of an epoch, with e = own
+    epoch counter (starts at ``init_epoch``, as WeightsSaver's), run ``validation.validate`` over ``steps`` batches of
+    ``valid_data`` when ``(e+1) % N == 0 and (e+1) >= min_epoch``.  The metrics go into the ``logs`` dict the hook was given (``fit``
+    keeps the ``val_*`` keys in its history), are appended to ``self.history`` as ``{"epoch": e+1, ...}``, and on rank 0 become one
+    row ``epoch, <metrics...>`` of ``<metrics_dir>/validation.csv`` -- header once, a resumed run appends; CSV and not the
+    reference's ``.xlsx``, because openpyxl may be absent.  ``validate_kw`` goes to ``validation.validate`` (draws_per_pass, alpha,
+    gamma, spacing).  Under data parallelism every rank holds this callback: ``validate`` is collective."""
+
+    def __init__(self, model, valid_data, steps, every_n_epochs, min_epoch, n_draws, train_obj, metrics_dir=None, init_epoch=0,
+                 rank: int = 0, world: int = 1, **validate_kw):
+        self.model = model
+        self.data = valid_data
+        self.steps = int(steps)
+        self.N = max(int(every_n_epochs), 1)
+        self.M = int(min_epoch)
+        self.n_draws = int(n_draws)
+        self.train_obj = train_obj
+        self.D = metrics_dir
+        self.epoch = int(init_epoch)
+        self.rank, self.world = int(rank), int(world)
+        self.kw = dict(validate_kw)
+        self.history = []
+
+    def _validate(self) -> dict:
+        from . import validation
+        return validation.validate(self.model, self.data, self.steps, self.train_obj, n_draws=self.n_draws, rank=self.rank,
+                                   world=self.world, **self.kw)
+
+    def _append_row(self, epoch: int, metrics: dict) -> None:
+        os.makedirs(self.D, exist_ok=True)
+        name = os.path.join(self.D, "validation.csv")
+        new = not os.path.exists(name) or os.path.getsize(name) == 0
+        with open(name, "a") as f:
+            if new:
+                f.write(",".join(["epoch"] + list(metrics)) + "\n")
+            f.write(",".join([str(epoch)] + [repr(float(v)) if isinstance(v, float) else str(v) for v in metrics.values()]) + "\n")
+
+    def on_epoch_end(self, epoch, logs=None):
+        if ((self.epoch + 1) % self.N == 0) and ((self.epoch + 1) >= self.M):
+            metrics = self._validate()
+            if metrics:                                   # (ranks other than 0 of a data-parallel run get {})
+                if logs is not None:
+                    logs.update(metrics)
+                self.history.append({"epoch": self.epoch + 1, **metrics})
+                if self.rank == 0:
+                    if self.D is not None:
+                        self._append_row(self.epoch + 1, metrics)
+                    print('Validation @ Epoch %03d: ' % (self.epoch + 1) + " - ".join(
+                        f"{k}: {v:.6f}" if isinstance(v, float) else f"{k}: {v}" for k, v in metrics.items()), flush=True)
         self.epoch += 1
 
 

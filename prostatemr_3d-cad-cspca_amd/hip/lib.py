@@ -117,6 +117,12 @@ M1_SD_U8, M1_SD_I32 = 0, 1
 M1_SD_STAGE_BORDER, M1_SD_STAGE_DISTANCE, M1_SD_STAGE_METRICS = 0, 1, 2
 M1_SD_MAX_CLASSES, M1_SD_MAX_TOLERANCES, M1_SD_MAX_LINE = 8, 4, 256
 
+# enum m1_val_dtype, the record of m1_val_score: 40 doubles = an 8-double header + 4 classes of 8 doubles
+M1_VAL_Y_F32, M1_VAL_Y_U8 = 0, 1
+M1_VAL_SLOTS, M1_VAL_MAX_K = 40, 4
+VAL_HEAD_KEYS = ("focal", "entropy_sum", "entropy_fg_sum", "n_voxels", "n_fg")
+VAL_CLASS_KEYS = ("sum_p", "sum_y", "sum_py", "n_pred", "n_true", "n_both", "p_max")
+
 # enum m1_label_objective / m1_feed_mode
 M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
 M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
@@ -227,6 +233,8 @@ SIGNATURES = {
     "m1_grad_norm": (_i, [_vp, _vp, _ll, _ll, _ll, _f, _f, _f, _f, _f, _i, _vp, _sz, _vp, _vp]),
     "m1_adam_amsgrad_ctl": (_i, [_vp] * 5 + [_ll, _ll, _ll, _f, _f, _f, _vp, _f, _f, _f, _vp, _f, _vp, _vp]),
     "m1_step_advance_ctl": (_i, [_vp, _vp, _vp]),
+    "m1_val_score_ws": (_sz, [_i, _ll, _i]),
+    "m1_val_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(_f), _f, _i, _ll, _i, _vp, _vp, _sz, _vp]),
     "m1_wgrad_defer": (_i, [_i]),
     "m1_wgrad_fold_pending": (_i, [_vp]),
     "m1_wgrad_fold_drop": (_i, []),

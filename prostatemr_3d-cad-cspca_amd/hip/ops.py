@@ -895,6 +895,56 @@ def mc_finish(sum_p: torch.Tensor, n: int):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Per-case scoring of a validation batch (validate.hip; validation.validate)
+# ---------------------------------------------------------------------------------------------------------
+def val_score_ws(B: int, voxels: int, K: int) -> int:
+    """Bytes of the workspace ``val_score`` needs for B cases of ``voxels`` voxels and K classes (host only)."""
+    return int(L.load().m1_val_score_ws(int(B), int(voxels), int(K)))
+
+
+def val_score(p: torch.Tensor, y: torch.Tensor, entropy: Optional[torch.Tensor] = None, alpha: Sequence[float] = (0.25, 0.75),
+              gamma: float = 2.0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One record of 40 doubles per case (m1_val_record_t, include/m1hip.h) from ``p`` (B,D,H,W,K) fp32, the one-hot ``y`` of the same
+    shape (uint8 or fp32; anything else is converted to fp32) and ``entropy`` (B,D,H,W) fp32 or None -> (B, 40) fp64 on the device.
+    Nothing is read back: ``read_val_records`` is the host read.  ``ws``: at least val_score_ws(B, D*H*W, K) bytes, 8-byte aligned."""
+    _no_grad_only("val_score")
+    if y.dtype not in (torch.float32, torch.uint8):
+        y = y.to(torch.float32)
+    _req(p, y, entropy, ws)
+    if p.dtype != torch.float32 or p.dim() < 3 or tuple(p.shape) != tuple(y.shape):
+        raise RuntimeError(f"val_score: p must be fp32 (B,...,K) and y of the same shape, got {p.dtype} {tuple(p.shape)} / {tuple(y.shape)}")
+    B, K = int(p.shape[0]), int(p.shape[-1])
+    V = p.numel() // max(B * K, 1)
+    if entropy is not None and (entropy.dtype != torch.float32 or tuple(entropy.shape) != tuple(p.shape[:-1])):
+        raise RuntimeError(f"val_score: entropy must be fp32 {tuple(p.shape[:-1])}, got {entropy.dtype} {tuple(entropy.shape)}")
+    if len(alpha) != K:
+        raise RuntimeError(f"val_score: {K} class weights expected, got {len(alpha)}")
+    lib = L.load()
+    if ws is None:
+        ws = torch.empty(max(val_score_ws(B, V, K), 8), dtype=torch.uint8, device=p.device)
+    rec = torch.empty((B, L.M1_VAL_SLOTS), dtype=torch.float64, device=p.device)
+    al = (C.c_float * K)(*[float(a) for a in alpha])
+    L.check(lib.m1_val_score(_p(p), _p(y), L.M1_VAL_Y_U8 if y.dtype == torch.uint8 else L.M1_VAL_Y_F32, _p(entropy), al, float(gamma),
+                             B, V, K, _p(rec), _p(ws), ws.numel() * ws.element_size(), _stream()), "m1_val_score")
+    return rec
+
+
+def read_val_records(records: torch.Tensor, K: int = L.M1_VAL_MAX_K) -> list:
+    """The records of ``val_score`` ((N, 40) fp64; several batches concatenated) on the host, one dict per case (synchronises): the
+    header's keys as floats, ints for the counts, and each class key as a list over the first ``K`` classes."""
+    w = records.detach().reshape(-1, L.M1_VAL_SLOTS).cpu().numpy()
+    out = []
+    for r in w:
+        d = {k: float(r[i]) for i, k in enumerate(L.VAL_HEAD_KEYS)}
+        d["n_voxels"], d["n_fg"] = int(d["n_voxels"]), int(d["n_fg"])
+        for j, k in enumerate(L.VAL_CLASS_KEYS):
+            col = [r[8 + 8 * c + j] for c in range(int(K))]
+            d[k] = [int(v) for v in col] if k.startswith("n_") else [float(v) for v in col]
+        out.append(d)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Focal loss on the softmax heads (losses.py:32-49)
 # ---------------------------------------------------------------------------------------------------------
 class _Focal(torch.autograd.Function):

@@ -24,9 +24,16 @@ What differs from the reference, and why (its harness bugs a
     (T:121) is outside the hot path: rejected loudly.  ``--LOSS_MODE region_boundary`` (T:125) trains with
     ``losses.SoftDicePlusBoundarySurface`` (GPU distance transform, no CPU step); under data parallelism each rank takes the
     loss of its own shard and the gradient all-reduce averages it, as MirroredStrategy does per replica.
-  * ``--UNET_PROBA_ITER`` ("Iterations of Probabilistic Inference During Validation", T:72) is parsed and NOT used: this trainer
-    does not validate.  What the flag stands for is ``n_draws`` of ``model.get_detect_model().predict_mc(x, n_draws)`` (mean and
-    entropy of n draws with fresh dropout masks and latent samples, unets/networks.py), for a caller's own validation loop.
+  * validation: the reference parses ``--VALID_XLSX_PREFIX``, ``--VALIDATE_PER_N_EPOCHS``, ``--VALIDATE_MIN_EPOCH``,
+    ``--UNET_PROBA_ITER`` and ``--METRICS_DIR`` and leaves the callbacks that would use them open (T:240-245).  Here ``--VALIDATE 1``
+    (a flag of this build, default 0: the trainer then makes exactly the calls it made before) adds ``callbacks.Validate`` after
+    ``WeightsSaver``: every ``VALIDATE_PER_N_EPOCHS`` epochs from ``VALIDATE_MIN_EPOCH`` on, ``validation.validate`` scores the
+    held-out cases with ``UNET_PROBA_ITER`` draws per case (``predict_mc``: fresh dropout masks and latent samples) and appends a row
+    to ``METRICS_DIR + NAME + '/F<fold>/validation.csv'``; the ``val_*`` numbers also enter ``fit``'s history.  The cases come from
+    ``VALID_XLSX_PREFIX<fold>.xlsx`` with ``--DATA_FEED sheet`` (``device_batches(mode='valid')``), else from ``--VALID_NPY_DIR`` or
+    ``--SYNTHETIC_VALID_SAMPLES`` synthetic cases seeded apart from the training cases.  The validation loss is the detection term
+    on the mean of the draws (no KL, no L2); validation does not move the model's dropout stream, so the weights of a run do not
+    depend on whether it validated.
   * checkpoints are ``model_weights_NNN.npz`` (callbacks.py); the fold-finished test uses the intended file name
     (the reference formats a set literal into it, T:103).
   * guarded optimiser step (flags of this build, all off by default; the reference passes none of them to its Adam, T:120):
@@ -134,6 +141,10 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--IMAGE_SPATIAL_DIMS', type=int, default=[20, 160, 160], nargs=3, help="(D,H,W) of synthetic volumes")
     prsr.add_argument('--COMPUTE_DTYPE', type=str, default="bf16", choices=["bf16", "fp32"], help="activation storage type")
     prsr.add_argument('--SEED', type=int, default=0)
+    # This build's train-time validation (callbacks.Validate): off by default
+    prsr.add_argument('--VALIDATE', type=int, default=0, help="1: validate every VALIDATE_PER_N_EPOCHS epochs from VALIDATE_MIN_EPOCH on")
+    prsr.add_argument('--VALID_NPY_DIR', type=str, default=None, help="--DATA_FEED cases: directory of held-out image_*.npy / label_*.npy pairs")
+    prsr.add_argument('--SYNTHETIC_VALID_SAMPLES', type=int, default=4, help="held-out synthetic cases per fold when no .npy directory is given")
     # This build's guarded optimiser step (optim.Adam): all off by default
     prsr.add_argument('--GRAD_CLIP_NORM', type=float, default=0.0, help="tf.keras global_clipnorm over all variables, 0 = off")
     prsr.add_argument('--GRAD_CLIP_VALUE', type=float, default=0.0, help="tf.keras clipvalue per gradient element, 0 = off")
@@ -228,6 +239,55 @@ def claim_fold_dir(fold_dir: str, resume: bool, rank: int = 0, world: int = 1) -
         dist.broadcast_object_list(flag, src=0)      # (also the barrier: nobody passes before rank 0 has decided)
     if flag[0]:
         raise Exception("Target Folder Already Exists! Either Remove It or Enable 'RESUME_TRAIN'.")
+
+
+class _Feed:
+    """A validation feed that starts from its first case on every pass: ``iter()`` builds a fresh generator."""
+
+    def __init__(self, make):
+        self.make = make
+
+    def __iter__(self):
+        return iter(self.make())
+
+
+def validation_feed(args, f: int, device, rank: int = 0, world: int = 1):
+    """(feed, steps) of fold f's held-out cases: the fold's validation sheet through ``device_batches(mode='valid')`` with
+    ``--DATA_FEED sheet``; else ``--VALID_NPY_DIR`` or ``--SYNTHETIC_VALID_SAMPLES`` synthetic cases from a generator seeded apart from
+    the training cases'.  The posterior's label channels are zeros (mode 'valid')."""
+    NUM_CLASSES = 2 if args.TRAIN_OBJ == 'lesion' else 3
+    prob = bool(args.UNET_PROBABILISTIC)
+    if args.DATA_FEED == 'sheet':
+        sheet = data_generators.fold_sheet(args.VALID_XLSX_PREFIX, f)
+        n = len(data_generators.read_sheet(sheet)["image_path"])
+        make = lambda: data_generators.device_batches(sheet, train_obj=args.TRAIN_OBJ, probabilistic=prob, mode='valid',  # noqa: E731
+                                                      batch_size=args.BATCH_SIZE, device=device, rank=rank, world=world)
+    else:
+        if args.VALID_NPY_DIR:
+            cases = load_npy_cases(args.VALID_NPY_DIR, NUM_CLASSES)
+        else:
+            rng = np.random.default_rng([args.SEED + 1000 * f, 0x76616C])       # (a stream of its own: never the training cases')
+            cases = [synthetic_case(rng, tuple(args.IMAGE_SPATIAL_DIMS), 3 if args.TRAIN_OBJ == 'lesion' else 1, NUM_CLASSES)
+                     for _ in range(args.SYNTHETIC_VALID_SAMPLES)]
+        n = len(cases)
+        make = lambda: batches(custom_data_generator(cases, probabilistic=prob, mode='valid'), args.BATCH_SIZE, device,  # noqa: E731
+                               rank, world)
+    return _Feed(make), int(math.ceil(n / args.BATCH_SIZE))
+
+
+def build_callbacks(args, f: int, model, fold_dir: str, init_epoch: int, valid_feed=None, rank: int = 0, world: int = 1) -> list:
+    """T:234-239: ``WeightsSaver``, and with ``--VALIDATE 1`` ``Validate`` behind it.  ``valid_feed()`` -> (feed, steps) is called only
+    when validation is on (the default run opens no validation data)."""
+    out = [cbs.WeightsSaver(model, weights_overwrite=bool(args.WEIGHTS_OVERWRITE), weights_dir=fold_dir,
+                            min_epoch=args.WEIGHTS_MIN_EPOCH, weights_num_epochs=args.STORE_WEIGHTS_PER_N_EPOCHS,
+                            init_epoch=init_epoch, rank=rank)]
+    if args.VALIDATE:
+        feed, steps = valid_feed()
+        out.append(cbs.Validate(model, feed, steps, every_n_epochs=args.VALIDATE_PER_N_EPOCHS, min_epoch=args.VALIDATE_MIN_EPOCH,
+                                n_draws=args.UNET_PROBA_ITER, train_obj=args.TRAIN_OBJ,
+                                metrics_dir=os.path.join(args.METRICS_DIR + args.NAME, 'F' + str(f + 1)), init_epoch=init_epoch,
+                                rank=rank, world=world, alpha=list(args.FOCAL_LOSS_ALPHA), gamma=args.FOCAL_LOSS_GAMMA))
+    return out
 
 
 # ---- one fold ---------------------------------------------------------------------------------------------------
@@ -356,9 +416,8 @@ def train_fold(args, f: int, device, rank: int = 0, world: int = 1):
         OPTIMIZER_SET.attach_reducer(ddp.GradReducer(world_size=world))
 
     # Callbacks (T:234-239) and training (T:253-259)
-    callbacks = [cbs.WeightsSaver(unet_model, weights_overwrite=bool(args.WEIGHTS_OVERWRITE), weights_dir=fold_dir,
-                                  min_epoch=args.WEIGHTS_MIN_EPOCH, weights_num_epochs=args.STORE_WEIGHTS_PER_N_EPOCHS,
-                                  init_epoch=init_epoch, rank=rank)]
+    callbacks = build_callbacks(args, f, unet_model, fold_dir, init_epoch, lambda: validation_feed(args, f, device, rank, world),
+                                rank, world)
     history = unet_model.fit(x=train_gen, epochs=args.NUM_EPOCHS, steps_per_epoch=steps_per_epoch, initial_epoch=init_epoch,
                              verbose=2 if rank == 0 else 0, callbacks=callbacks, use_multiprocessing=True)
     return unet_model, history, callbacks[0]

@@ -222,8 +222,12 @@ class LoadableModel(nn.Module):
                 history.setdefault(k, []).append(v)
             if verbose:
                 print(f"Epoch {epoch + 1}/{epochs} - {time.time() - t0:.1f}s - " + " - ".join(f"{k}: {v:.6f}" for k, v in logs.items()), flush=True)
+            own = set(logs)
             for cb in callbacks:
                 getattr(cb, "on_epoch_end", lambda *a, **k: None)(epoch, logs)
+            for k, v in logs.items():                     # what a callback added (callbacks.Validate), as Keras' History keeps it:
+                if k not in own and k.startswith("val_"):  # epochs without validation get no entry
+                    history.setdefault(k, []).append(v)
             if steps_per_epoch is None:
                 it = iter(x)
             if self.stop_training:
