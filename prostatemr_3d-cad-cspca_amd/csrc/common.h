@@ -107,6 +107,22 @@ static inline int m1_grid_for(long long per, int cg) {
     g = (g + need - 1) / need * need;
     return (int)g;
 }
+// The same for a launch over N samples (gridDim.y = N): about M1_EW_TOTAL blocks in the WHOLE launch at most.  The per-sample cap alone
+// puts up to 2048 x N blocks behind a stacked batch, and every thread of the SE / InstanceNorm kernels starts with the 32 - 104 loads of
+// its per-channel constants: at N = 4 a thread ran ONE or two vectors behind them.  768 = 3 blocks per CU, one round of the SE apply
+// kernel (3 waves per SIMD).  Alone on the GPU 1536 is as fast or faster per kernel; in the replayed C3 step, where these kernels share
+// the GPU with the side streams' kernels, 768 is the fastest of 768 / 1024 / 1536 / 3072 (profiles/se_stream_kernels.txt).
+// 0: the per-sample cap only.
+static inline int m1_grid_for_n(long long per, int cg, int N) {
+    const int g = m1_grid_for(per, cg);
+    const int tot = M1_CFG("M1_EW_TOTAL", 768);
+    if (tot <= 0 || N <= 1) return g;
+    long long a = cg, b = 256; while (b) { long long t = a % b; a = b; b = t; }
+    const long long need = cg / a;
+    long long gn = tot / N; if (gn < 1) gn = 1;
+    gn = (gn + need - 1) / need * need;
+    return (int)(gn < g ? gn : g);
+}
 __device__ __forceinline__ float lrelu_f(float x, float slope) { return x >= 0.f ? x : slope * x; }
 __device__ __forceinline__ float lrelu_g(float x, float slope) { return x >= 0.f ? 1.f : slope; }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }

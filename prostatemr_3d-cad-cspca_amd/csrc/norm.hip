@@ -101,12 +101,12 @@ static int apply_impl(const void* x, const float* stats, const float* gamma, con
     long long per;
     if (C % VW == 0) {
         per = V * (C / VW);
-        int gx = m1_grid_for(per, C / VW);
+        int gx = m1_grid_for_n(per, C / VW, N);
         hipLaunchKernelGGL((in_apply_kernel<T, VW>), dim3(gx, N), dim3(256), 0, st, (const T*)x, stats, gamma, beta,
                            slope, (T*)y, V, C);
     } else {
         per = V * C;
-        int gx = m1_grid_for(per, C);
+        int gx = m1_grid_for_n(per, C, N);
         hipLaunchKernelGGL((in_apply_kernel<T, 1>), dim3(gx, N), dim3(256), 0, st, (const T*)x, stats, gamma, beta,
                            slope, (T*)y, V, C);
     }
@@ -201,11 +201,11 @@ static int bwd_from_partials(const void* x, const float* stats, const float* gam
     constexpr int VW = sizeof(T) == 2 ? 8 : 4;
     if (C % VW == 0) {
         long long per = V * (C / VW);
-        int gx = m1_grid_for(per, C / VW);
+        int gx = m1_grid_for_n(per, C / VW, N);
         hipLaunchKernelGGL((in_bwd_apply_kernel<T, VW>), dim3(gx, N), dim3(256), 0, st, (const T*)x, (const T*)dy, stats, gamma, beta, slope, sums, (T*)dx, V, C);
     } else {
         long long per = V * C;
-        int gx = m1_grid_for(per, C);
+        int gx = m1_grid_for_n(per, C, N);
         hipLaunchKernelGGL((in_bwd_apply_kernel<T, 1>), dim3(gx, N), dim3(256), 0, st, (const T*)x, (const T*)dy, stats, gamma, beta, slope, sums, (T*)dx, V, C);
     }
     return m1_check_launch();
@@ -234,12 +234,12 @@ static int bwd_impl(const void* x, const float* stats, const float* gamma, const
     constexpr int VW = sizeof(T) == 2 ? 8 : 4;
     if (C % VW == 0) {
         long long per = V * (C / VW);
-        int gx = m1_grid_for(per, C / VW);
+        int gx = m1_grid_for_n(per, C / VW, N);
         hipLaunchKernelGGL((in_bwd_apply_kernel<T, VW>), dim3(gx, N), dim3(256), 0, st, (const T*)x, (const T*)dy,
                            stats, gamma, beta, slope, sums, (T*)dx, V, C);
     } else {
         long long per = V * C;
-        int gx = m1_grid_for(per, C);
+        int gx = m1_grid_for_n(per, C, N);
         hipLaunchKernelGGL((in_bwd_apply_kernel<T, 1>), dim3(gx, N), dim3(256), 0, st, (const T*)x, (const T*)dy,
                            stats, gamma, beta, slope, sums, (T*)dx, V, C);
     }

@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(256, 3) se_combine_fwd_kernel(const T* __restr
     const size_t base_in = (size_t)n * p.V * F, base = (size_t)n_out * p.V * F;          // (base: output / dropout-stream / mask index)
     uint64_t seed, rbase; se_rng(p, seed, rbase);
     const float keep_scale = p.drop_rate > 0.f ? 1.f / (1.f - p.drop_rate) : 1.f;
-    // the launch keeps gridDim.x*blockDim.x a multiple of the channel groups (m1_grid_for): a thread's channels never change and
+    // the launch keeps gridDim.x*blockDim.x a multiple of the channel groups (m1_grid_for_n): a thread's channels never change and
     // their 9 parameters live in registers (re-loaded per vector they were 72 dword loads beside 2 data loads: TA bound)
     const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
     const int c0 = (int)(i0 % cg) * VEC;
@@ -441,18 +441,18 @@ static int se_fwd_impl(const void* y3, const void* y4, const SeParams& p, void* 
     const int N = p.dupB ? 2 * N_in : N_in;              // blocks walk the OUTPUT samples (SeParams::dupB: two per input sample)
     if (p.identity4) {                                   // network_blocks.py:63 false branch: its own instantiations (compile-time constants)
         if (p.F % VW == 0)
-            hipLaunchKernelGGL((se_combine_fwd_kernel<T, VW, true>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st, (const T*)y3,
+            hipLaunchKernelGGL((se_combine_fwd_kernel<T, VW, true>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st, (const T*)y3,
                                (const T*)y4, p, (T*)out);
         else
-            hipLaunchKernelGGL((se_combine_fwd_kernel<T, 1, true>), dim3(m1_grid_for(p.V * p.F, p.F), N), dim3(256), 0, st, (const T*)y3,
+            hipLaunchKernelGGL((se_combine_fwd_kernel<T, 1, true>), dim3(m1_grid_for_n(p.V * p.F, p.F, N), N), dim3(256), 0, st, (const T*)y3,
                                (const T*)y4, p, (T*)out);
         return m1_check_launch();
     }
     if (p.F % VW == 0)
-        hipLaunchKernelGGL((se_combine_fwd_kernel<T, VW>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st, (const T*)y3,
+        hipLaunchKernelGGL((se_combine_fwd_kernel<T, VW>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st, (const T*)y3,
                            (const T*)y4, p, (T*)out);
     else
-        hipLaunchKernelGGL((se_combine_fwd_kernel<T, 1>), dim3(m1_grid_for(p.V * p.F, p.F), N), dim3(256), 0, st, (const T*)y3,
+        hipLaunchKernelGGL((se_combine_fwd_kernel<T, 1>), dim3(m1_grid_for_n(p.V * p.F, p.F, N), N), dim3(256), 0, st, (const T*)y3,
                            (const T*)y4, p, (T*)out);
     return m1_check_launch();
 }
@@ -475,13 +475,13 @@ static int se_bwd_impl(const void* y3, const void* y4, const void* dout, const S
         if (rc) return rc;
         rc = m1_reduce_finalize_params_launch<5>(ws, N, p.F, nchunks, sums, po, st); if (rc) return rc;
         if (masked)
-            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, true, 2, true>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st,
+            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, true, 2, true>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st,
                                (const T*)y3, (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
         else if (p.F % VW == 0)
-            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, false, 2, true>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st,
+            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, false, 2, true>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st,
                                (const T*)y3, (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
         else
-            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, 1, false, 2, true>), dim3(m1_grid_for(p.V * p.F, p.F), N), dim3(256), 0, st, (const T*)y3,
+            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, 1, false, 2, true>), dim3(m1_grid_for_n(p.V * p.F, p.F, N), N), dim3(256), 0, st, (const T*)y3,
                                (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
         return m1_check_launch();
     }
@@ -493,10 +493,10 @@ static int se_bwd_impl(const void* y3, const void* y4, const void* dout, const S
         if (rc) return rc;
         rc = m1_reduce_finalize_params_launch<5>(ws, N, p.F, nchunks, sums, po, st); if (rc) return rc;
         if (masked)
-            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, true, 2, false, true>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st,
+            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, true, 2, false, true>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st,
                                (const T*)y3, (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
         else
-            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, false, 2, false, true>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st,
+            hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, false, 2, false, true>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st,
                                (const T*)y3, (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
         return m1_check_launch();
     }
@@ -504,18 +504,15 @@ static int se_bwd_impl(const void* y3, const void* y4, const void* dout, const S
     else { SeBwdF<T> f{(const T*)y3, (const T*)y4, (const T*)dout, p}; rc = m1_reduce_nc_launch<5>(f, N, p.V, p.F, ws, st); }
     if (rc) return rc;
     rc = m1_reduce_finalize_params_launch<5>(ws, N, p.F, nchunks, sums, po, st); if (rc) return rc;
-    int w3 = M1_CFG("M1_SE_BWD_W3", 0);
-    if (masked && w3)       // 3 waves per SIMD at the price of 4 spilled registers (measured: see DESIGN 5)
-        hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, true, 3>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st,
-                           (const T*)y3, (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
-    else if (masked)
-        hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, true>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st,
+    // (the masked kernel takes 164 registers with or without a 3-wave launch bound: 3 waves per SIMD either way, no separate variant)
+    if (masked)
+        hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW, true>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st,
                            (const T*)y3, (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
     else if (p.F % VW == 0)
-        hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW>), dim3(m1_grid_for(p.V * (p.F / VW), p.F / VW), N), dim3(256), 0, st,
+        hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, VW>), dim3(m1_grid_for_n(p.V * (p.F / VW), p.F / VW, N), N), dim3(256), 0, st,
                            (const T*)y3, (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
     else
-        hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, 1>), dim3(m1_grid_for(p.V * p.F, p.F), N), dim3(256), 0, st, (const T*)y3,
+        hipLaunchKernelGGL((se_combine_bwd_apply_kernel<T, 1>), dim3(m1_grid_for_n(p.V * p.F, p.F, N), N), dim3(256), 0, st, (const T*)y3,
                            (const T*)y4, (const T*)dout, p, sums, (T*)dy3, (T*)dy4);
     return m1_check_launch();
 }

@@ -9,7 +9,7 @@ rows = list(csv.DictReader(open(path)))
 for r in rows:
     r["s"] = int(r["Start_Timestamp"]); r["e"] = int(r["End_Timestamp"])
 rows.sort(key=lambda r: r["s"])
-ad = [i for i, r in enumerate(rows) if r["Kernel_Name"].startswith("adam_amsgrad")]
+ad = [i for i, r in enumerate(rows) if "adam_amsgrad" in r["Kernel_Name"]]          # ("void adam_amsgrad_kernel<false>(...)" since the guarded step)
 if len(ad) < 2:
     sys.exit("fewer than two optimiser launches in the trace")
 k = which if which >= 0 else len(ad) - 2
