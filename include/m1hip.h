@@ -10,9 +10,9 @@
  *     workspaces; no device allocation, no hidden synchronisation; every launch goes to the caller's
  *     hipStream_t (graph-capturable: no memset / memcpy nodes, zero fills are kernels).
  *   - process-global host state the library DOES keep (all of it behind mutexes, none of it device memory):
- *     the tuning-switch table (m1_config_*), the queue of deferred weight-gradient folds between m1_wgrad_defer(1)
- *     and m1_wgrad_fold_pending / _drop (the queued jobs point into caller-owned workspaces, which the caller keeps
- *     alive until then), the test hook m1_set_force_direct, the opt-in profiler (m1_prof_*) and the opt-in
+ *     the tuning-switch table (m1_config_*), the ONE queue of deferred weight-gradient folds and transposed-conv bias
+ *     sums between m1_wgrad_defer(1) and m1_wgrad_fold_pending / _drop (the queued jobs point into caller-owned
+ *     workspaces and, for the bias sums, into d(out); the caller keeps both alive until then), the test hook m1_set_force_direct, the opt-in profiler (m1_prof_*) and the opt-in
  *     kernel-choice log (m1_debug_kernels).  One thread drives the library at a time per process.
  *   - results are bit-reproducible run to run in the default configuration: every reduction across blocks goes
  *     through per-split partials folded in a fixed order.  Floating-point atomics remain compiled in behind
@@ -742,9 +742,13 @@ int m1_val_score(const float* p, const void* y, int y_dtype, const float* entrop
  * gradients inside each op).  m1_conv3d_wgrad / m1_convT3d_wgrad split the voxels over blocks, every block stores its partial
  * tile into a copy inside `ws`, and a fold kernel adds the copies into dw / db in a fixed order.  After m1_wgrad_defer(1) the
  * weight-gradient entry points QUEUE that fold instead of launching it (process-wide, host side); m1_wgrad_fold_pending runs
- * everything queued in a few batched launches on `stream` -- the caller keeps every `ws` alive and orders `stream` behind the
- * weight-gradient launches until then; dw / db are incomplete before.  m1_wgrad_fold_drop forgets the queue (gradients
- * discarded).  A second fold into the same block of dw while one is queued first runs the queue on that call's stream. */
+ * everything queued in a few batched launches on `stream` -- the caller orders `stream` behind the weight-gradient launches and
+ * keeps alive until then every `ws` and, for m1_convT3d_wgrad with a db, also d(out): the bias gradient of a transposed conv is
+ * a column sum of d(out), queued with the folds and READ at m1_wgrad_fold_pending.  dw / db are incomplete before.
+ * m1_wgrad_fold_drop forgets the queue (gradients discarded).  The same parameter twice inside one window: a second fold into
+ * a block of dw that already has one queued is NOT queued and does not run the queue -- it is launched at once on its own call's
+ * stream (the queue may hold work of streams that call is not ordered behind) and the queued one still runs at
+ * m1_wgrad_fold_pending; a second column sum into a db that has one queued is computed at once, in place, likewise. */
 int m1_wgrad_defer(int on);
 int m1_wgrad_fold_pending(void* stream);
 int m1_wgrad_fold_drop(void);

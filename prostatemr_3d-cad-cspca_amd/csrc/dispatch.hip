@@ -5,7 +5,7 @@
 //   wgrad_ws       the regions of a weight gradient's `ws`
 //   WG_LADDER      the order in which the weight-gradient kernels are tried
 #include "common.h"
-#include "gather.h"
+#include "wgrad_fold.h"
 #include "reduce.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -303,7 +303,7 @@ __global__ void __launch_bounds__(256) stem_fold_kernel(const float* __restrict_
 }
 
 // Scratch for the per-split partial copies of a weight gradient (+ bias sums): compact copies of ONE concat member's block
-// ([tap][C_member][Cout] + Cout floats), up to 512 of them, at most 64 MB.  It lives in the caller's wgrad workspace -- one region
+// ([tap][C_member][Cout] + Cout floats), up to M1_WG_MAX_COPIES of them, at most 64 MB.  It lives in the caller's wgrad workspace -- one region
 // per call, so weight gradients that run concurrently on different streams never share it (the library keeps no device memory
 // of its own).  All weight-gradient kernels fold copies in a fixed order instead of using floating-point atomics.
 static size_t wgrad_rx_bytes(const m1_conv_desc_t* d) {
@@ -311,8 +311,8 @@ static size_t wgrad_rx_bytes(const m1_conv_desc_t* d) {
     size_t cmax = 8;                                           // (the padded stem runs as an 8-channel member)
     for (int i = 0; i < d->nsrc; ++i) if ((size_t)d->src[i].C > cmax) cmax = d->src[i].C;
     const size_t other = cmax > (size_t)d->Cout ? cmax : (size_t)d->Cout;      // (transposed conv: the roles of the two sides swap)
-    const size_t stride = taps * cmax * d->Cout + other;
-    size_t b = 512 * stride * sizeof(float);
+    const size_t stride = (size_t)m1_wg_copy_floats(taps, cmax, d->Cout, other);
+    size_t b = M1_WG_MAX_COPIES * stride * sizeof(float);
     const long long cap = (long long)M1_CFG("M1_WG_RX_MB", 64) << 20;
     if (b > (size_t)cap) b = (size_t)cap;
     if (b < 2 * stride * sizeof(float)) b = 2 * stride * sizeof(float);
@@ -657,7 +657,7 @@ static int wgrad_common(const m1_conv_desc_t* d, bool T, const void* dy, float* 
     if (db && !fuse_db) {
         if (!ws) return M1_ERR_WORKSPACE;
         const long long Vd = (long long)q.OD * q.OH * q.OW;
-        if (!g_force_direct && m1_fold_defer_get() && m1_colsum_defer(dy, d->N, Vd, d->Cout, d->dtype, db, (float*)ws, accumulate)) return M1_OK;
+        if (!g_force_direct && m1_colsum_defer(dy, d->N, Vd, d->Cout, d->dtype, db, (float*)ws, accumulate)) return M1_OK;
         return m1_colsum_internal(dy, d->N, Vd, d->Cout, d->dtype, db, (float*)ws, st, accumulate);
     }
     return M1_OK;

@@ -70,10 +70,6 @@ bool m1_tf_wgrad_supported(const WgradSpec& g);      // tap-fused variant (wgrad
 // nothing was launched, the caller takes the per-tap kernel instead.
 int m1_tf_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st);
 int m1_tf_wgrad_multi(const WgradSpec& g, long long nw, int nb, hipStream_t st, int nmem, const void* const* Am, const int* a_offs, long long rx_mem);
-// partial-copy scratch (the spec's rx region when it holds `floats`, else nullptr = take the atomic path) and the fold of
-// `ncopies` copies of stride `stride` floats into g.R / g.bsum (bias sums sit at offset nw inside a copy)
-static inline float* m1_wg_rx_get(const WgradSpec& g, long long floats) { return (g.rx && g.rx_floats >= floats) ? g.rx : nullptr; }
-int m1_wg_rx_finish(float* rx, long long stride, int ncopies, const WgradSpec& g, long long nw, hipStream_t st);
 int m1_mfma_wgrad_ex(const WgradSpec& g, long long nw, int nb, hipStream_t st);
 bool m1_tap_wgrad_supported(const WgradSpec& g);     // per-tap kernel on the transpose read (wgrad_tap.hip), >= 64 channels
 int m1_tap_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st);
@@ -88,12 +84,5 @@ int m1_t3s_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st);
 bool m1_pwf_wgrad_supported(const WgradSpec& g);
 int m1_pwf_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st);
 int m1_colsum_internal(const void* x, int N, long long V, int C, int dtype, float* out, float* ws, hipStream_t st, int accumulate);
-
-// deferred-fold switch of m1_wg_rx_finish (wgrad_tf.hip): returns the previous setting
 long long m1_stats_rows_cap(long long V);       // partial rows per sample of a statistics workspace (norm.hip)
-int m1_fold_defer_set(int on);
-int m1_fold_defer_get();
-// deferred bias gradients of the transposed convs (norm.hip): queued under m1_wgrad_defer, launched by m1_wgrad_fold_pending
-bool m1_colsum_defer(const void* x, int N, long long V, int C, int dtype, float* out, float* ws, int accumulate);
-int m1_colsum_launch_pending(hipStream_t st);
-void m1_colsum_drop_pending();
+// (the partial-copy plan, the fold and its deferred queue: wgrad_fold.h)

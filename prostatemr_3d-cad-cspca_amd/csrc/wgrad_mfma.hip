@@ -8,7 +8,7 @@
 // forward kernel uses; the fragment reads / MFMA issue are then identical to conv_mfma.hip.
 // One block = one (tap, a-tile, b-tile, voxel-split); partial results are combined with fp32 atomics in L2.
 #include "common.h"
-#include "gather.h"
+#include "wgrad_fold.h"
 #include "cdna4.h"
 #include <stdlib.h>
 
@@ -228,6 +228,10 @@ bool m1_mfma_wgrad_supported(const WgradSpec& g) {
     return (long long)g.N * g.BD * g.BH * g.BW < (1ll << 31) - 4096;       // 32-bit voxel arithmetic in the kernel
 }
 
+// copies: the launcher bounds its splits itself (4 K-steps of voxels each, rounded UP, and vox_per_split re-derived after every
+// clamp); no ceiling of their own (the rx region is sized for M1_WG_MAX_COPIES)
+static const WgCopyRule WG_COPIES = {0, 0, 0, WG_SHORT_FALLBACK};
+
 template <typename T, int TA, int TB>
 static int launch_wg(WgP p, hipStream_t st) {
     constexpr int KB = (TA + TB) <= 64 ? 8 : ((TA + TB) <= 128 ? 4 : 2);
@@ -252,19 +256,15 @@ static int launch_wg(WgP p, hipStream_t st) {
     // CB bias sums) and m1_wg_rx_finish folds the copies in a fixed order -- no floating-point atomics, so the weight gradient is
     // bit-reproducible run to run (M1_WG_DET=0 restores the atomic path for large blocks).  Fewer splits when the caller's
     // scratch holds fewer copies; one split needs none (a single add per element and launch is ordered by the stream).
-    bool partial = false;
-    const long long stride = (long long)taps * p.CA * p.CB + p.CB;
-    p.rx_stride = stride; p.rx_bias = (long long)taps * p.CA * p.CB;
     int det = M1_CFG("M1_WG_DET", 1);
     const bool small = (long long)taps * p.CA * p.CB <= 32768 && splits >= 24;
-    if (splits >= 2 && (det || small)) {
-        long long fit = p.rx ? p.rx_floats / stride : 0;
-        if (fit >= 2) {
-            if (splits > fit) { splits = fit; vps = cdiv_ll(cdiv_ll(TV, splits), KS) * KS; splits = cdiv_ll(TV, vps); p.vox_per_split = vps; grid.z = (unsigned)splits; }
-            if (splits >= 2) { p.Rx = p.rx; partial = true; }
-        } else if (det) { splits = 1; vps = cdiv_ll(TV, KS) * KS; p.vox_per_split = vps; grid.z = 1; }
-    }
-    if (!partial) { p.Rx = nullptr; }
+    const WgCopies c = m1_wg_copies(p, taps, splits, 0, WG_COPIES, det || small);
+    p.rx_stride = c.stride; p.rx_bias = c.rx_bias; p.Rx = nullptr;
+    if (c.Rx) {
+        if (c.nsplit < splits) { splits = c.nsplit; vps = cdiv_ll(cdiv_ll(TV, splits), KS) * KS; splits = cdiv_ll(TV, vps); p.vox_per_split = vps; grid.z = (unsigned)splits; }
+        if (splits >= 2) p.Rx = c.Rx;
+    } else if (det && splits >= 2) { splits = 1; vps = cdiv_ll(TV, KS) * KS; p.vox_per_split = vps; grid.z = 1; }
+    const bool partial = p.Rx != nullptr;
     int xr = M1_CFG("M1_WG_XCD", 1);
     p.xcd_total = 0; p.xcd_gx = (int)grid.x; p.xcd_gy = (int)grid.y; p.xcd_gz = (int)grid.z;
     if (xr && (long long)grid.x * grid.y > 1 && splits > 1) {
@@ -276,7 +276,7 @@ static int launch_wg(WgP p, hipStream_t st) {
         hipLaunchKernelGGL((wgrad_mfma_kernel<T, TA, TB, KB>), grid, dim3(256), 0, st, p);
     }
     int rc = m1_check_launch(); if (rc) return rc;
-    if (partial) return m1_wg_rx_finish(p.Rx, stride, (int)splits, p, p.rx_bias, st);
+    if (partial) return m1_wg_rx_finish(p.Rx, c.stride, (int)splits, p, p.rx_bias, st);
     return M1_OK;
 }
 

@@ -28,7 +28,7 @@
 // wgrad_t3f_kernel below is the fp32 variant of the same block on v_mfma_f32_32x32x2_f32 (plain dword fragment reads, two stages);
 // wgrad_t3s.hip holds the fp32 kernels for layers with few channels and for pointwise layers.
 #include "common.h"
-#include "gather.h"
+#include "wgrad_fold.h"
 #include "cdna4.h"
 #include <stdlib.h>
 
@@ -547,19 +547,18 @@ static bool t3_plan(const WgradSpec& g, T3P& p) {
     }
     if (!kws) { if (g.BW <= 32) kws = g.BW; else { for (int c = 28; c >= 8; c -= 4) if (g.BW % c == 0) { kws = c; break; } } }
     if (!kws) return false;
-    p.KWs = kws; p.TH = T3_KT / kws;
+    if (!m1_wg_ktiles(g, T3_KT, kws, 8, p)) return false;
     if (p.TH + 2 > 255 || p.KWs + 2 > 255) return false;
     const int nA = s1 ? ((p.TH + 2) * (p.KWs + 2) + 7) / 8 : (4 * (p.TH + 1) * (p.KWs + 2) + 7) / 8;
     if (!f32 && nA > (s1 ? 18 : 60)) return false;             // (the kernel's fixed piece slots: 24 / 36 / 60 pieces for the A tiles)
     if (f32 && !(kws == 8 || kws == 16 || kws == 32)) return false;
-    if (2 * p.TH + 1 > 255 || 2 * p.KWs + 3 > 255) return false;
-    p.tiles_w = g.BW / p.KWs; p.tiles_h = (g.BH + p.TH - 1) / p.TH;
-    const long long nt = (long long)g.N * g.BD * p.tiles_h * p.tiles_w;
-    if (nt >= (1ll << 30) || nt < 8) return false;
-    p.ntiles = (int)nt;
-    return true;
+    return 2 * p.TH + 1 <= 255 && 2 * p.KWs + 3 <= 255;
 }
 bool m1_t3_wgrad_supported(const WgradSpec& g) { T3P p; return t3_plan(g, p); }
+
+// copies: >= 8 K-tiles each (a block's prologue and its partial tiles must amortise), no ceiling of their own (the rx region is
+// sized for M1_WG_MAX_COPIES)
+static const WgCopyRule T3_COPIES = {8, 0, 0, WG_SHORT_ERROR};
 
 // `nmem` members of one Conv3D concat at once (nmem = 1: Am / a_offs may be null): member m = (Am[m], a_off a_offs[m]), all with
 // g.CA channels; copies of member m live at g.rx + m * rx_mem
@@ -576,13 +575,9 @@ int m1_t3_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st, int nm
     const int gx = bigb ? g.CB / 128 : g.CB / 64, gzu = bigb ? p.nunits : (p.nunits + 1) / 2;
     const long long per_split = (long long)gx * gzu * g.kd;    // blocks per voxel split
     int tgt = M1_CFG("M1_T3_BLOCKS", 256);      // one block per CU
-    long long nsplit = tgt / per_split; if (nsplit < 1) nsplit = 1;
-    const long long nloc = (long long)g.kd * 9 * g.CA * g.CB;
-    const long long stride = nloc + g.CB;                      // compact copy of one member's block (+ bias sums)
-    if (!g.rx || g.rx_floats < stride) return M1_ERR_WORKSPACE;
-    if (nsplit * stride > g.rx_floats) nsplit = g.rx_floats / stride;
-    if (nsplit > p.ntiles / 8) nsplit = p.ntiles / 8;          // >= 8 K-tiles per block: its prologue and its partial tiles must amortise
-    if (nsplit < 1) nsplit = 1;
+    const WgCopies c = m1_wg_copies(g, g.kd * 9, tgt / per_split, p.ntiles, T3_COPIES);
+    if (c.rc) return c.rc;
+    const long long nsplit = c.nsplit, stride = c.stride, nloc = c.rx_bias;
     // too small to fill the chip at that depth (single layers of the (10,20,20) level): the per-tap kernel, with 27 x more
     // blocks per voxel split, is the better fit
     int minb = M1_CFG("M1_T3_MIN_BLOCKS", 128);
@@ -612,11 +607,5 @@ int m1_t3_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st, int nm
     m1_note_kernel(f32 ? "wgrad_t3f:kws%d:big%d" : (s2 ? "wgrad_t3:s2:kws%d:big%d" : "wgrad_t3:kws%d:big%d"), p.KWs, (int)bigb);
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)nsplit, (unsigned)(gzu * g.kd)), dim3(T3_THREADS), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;
-    for (int m = 0; m < nmem; ++m) {                      // one fold per member (its own block of R; the bias sums ride on member 0)
-        WgradSpec gm = g;
-        if (nmem > 1) gm.a_off = a_offs[m];
-        if (m) gm.bsum = nullptr;
-        rc = m1_wg_rx_finish(p.Rx + (long long)m * p.rx_mem, stride, (int)nsplit, gm, nloc, st); if (rc) return rc;
-    }
-    return M1_OK;
+    return m1_wg_fold_members(p.Rx, p.rx_mem, stride, (int)nsplit, g, nloc, nmem, a_offs, st);
 }

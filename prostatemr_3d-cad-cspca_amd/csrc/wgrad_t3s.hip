@@ -13,7 +13,7 @@
 //   LDS when the block is done;
 // * tile table, fixed DMA piece slots, per-split partial copies + fixed-order fold as in wgrad_t3.hip (no float atomics).
 #include "common.h"
-#include "gather.h"
+#include "wgrad_fold.h"
 #include "cdna4.h"
 #include <stdlib.h>
 
@@ -235,21 +235,20 @@ static bool ts_plan(const WgradSpec& g, TSP& p, int* kws_out) {
     // at the deep levels) only this kernel
     if (nau * nbu > (s2 ? 128 : 32)) return false;
     if ((long long)(g.AH + 4) * g.AW * g.CA * 4 >= (1ll << 31) - 4096 || (long long)(g.BH + 20) * g.BW * g.CB * 4 >= (1ll << 31) - 4096) return false;
-    int kws = g.BW % 32 == 0 ? 32 : (g.BW % 16 == 0 ? 16 : 8);
-    const int KT = s2 ? TS_KT / 2 : TS_KT;
+    WgKTiles t;
+    if (!m1_wg_ktiles(g, s2 ? TS_KT / 2 : TS_KT, m1_wg_kws(g.BW, 8), 4, t)) return false;
     p = TSP{};
     p.A = (const float*)g.A; p.B = (const float*)g.B;
     p.CA = g.CA; p.CB = g.CB; p.AD = g.AD; p.AH = g.AH; p.AW = g.AW; p.BD = g.BD; p.BH = g.BH; p.BW = g.BW; p.N = g.N;
     p.pd = g.pd; p.ph = g.ph; p.pw = g.pw; p.KD = g.kd; p.sd = g.sd;
-    const int TH = KT / kws;
-    p.tiles_w = g.BW / kws; p.tiles_h = (g.BH + TH - 1) / TH;
-    const long long nt = (long long)g.N * g.BD * p.tiles_h * p.tiles_w;
-    if (nt >= (1ll << 30) || nt < 4) return false;
-    p.ntiles = (int)nt; p.nau = nau;
-    *kws_out = kws;
+    p.tiles_w = t.tiles_w; p.tiles_h = t.tiles_h; p.ntiles = (int)t.ntiles; p.nau = nau;
+    *kws_out = t.KWs;
     return true;
 }
 bool m1_t3s_wgrad_supported(const WgradSpec& g) { TSP p; int k; return ts_plan(g, p, &k); }
+
+// copies: >= 4 K-tiles each, at most M1_WG_MAX_COPIES
+static const WgCopyRule TS_COPIES = {4, M1_WG_MAX_COPIES, 0, WG_SHORT_ERROR};
 
 int m1_t3s_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     TSP p; int kws;
@@ -258,14 +257,9 @@ int m1_t3s_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     const int nbu = (g.CB + TLh - 1) / TLh;
     const long long per_split = (long long)nbu * p.nau * g.kd;
     int tgt = M1_CFG("M1_T3S_BLOCKS", 256);
-    long long nsplit = tgt / per_split; if (nsplit < 1) nsplit = 1;
-    const long long nloc = (long long)g.kd * 9 * g.CA * g.CB;
-    const long long stride = nloc + g.CB;
-    if (!g.rx || g.rx_floats < stride) return M1_ERR_WORKSPACE;
-    if (nsplit * stride > g.rx_floats) nsplit = g.rx_floats / stride;
-    if (nsplit > p.ntiles / 4) nsplit = p.ntiles / 4;          // >= 4 K-tiles per block
-    if (nsplit > 512) nsplit = 512;
-    if (nsplit < 1) nsplit = 1;
+    const WgCopies c = m1_wg_copies(g, g.kd * 9, tgt / per_split, p.ntiles, TS_COPIES);
+    if (c.rc) return c.rc;
+    const long long nsplit = c.nsplit, stride = c.stride, nloc = c.rx_bias;
     p.nsplit = (int)nsplit;
     p.Rx = g.rx; p.rx_stride = stride; p.rx_bias = nloc;
     p.want_bsum = g.bsum != nullptr;
@@ -422,6 +416,8 @@ bool m1_pwf_wgrad_supported(const WgradSpec& g) {
     if ((long long)PW_KT * (g.CA > g.CB ? g.CA : g.CB) * 4 >= (1ll << 31) - 4096) return false;
     return ((g.CA + 63) / 64) * ((g.CB + 63) / 64) <= 64;
 }
+// copies: >= 2 K-tiles each, at most M1_WG_MAX_COPIES
+static const WgCopyRule PW_COPIES = {2, M1_WG_MAX_COPIES, 0, WG_SHORT_ERROR};
 int m1_pwf_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     if (!m1_pwf_wgrad_supported(g)) return M1_ERR_UNSUPPORTED;
     PWP p{};
@@ -430,14 +426,10 @@ int m1_pwf_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     p.ntiles = (int)((p.V + PW_KT - 1) / PW_KT);
     const int nau = (g.CA + 63) / 64, nbu = (g.CB + 63) / 64;
     int tgt = M1_CFG("M1_PWF_BLOCKS", 256);     // one block per CU (128 KB of LDS)
-    long long nsplit = tgt / (nau * nbu); if (nsplit < 1) nsplit = 1;
-    const long long nloc = (long long)g.CA * g.CB, stride = nloc + g.CB;
-    if (!g.rx || g.rx_floats < stride) return M1_ERR_WORKSPACE;
-    if (nsplit * stride > g.rx_floats) nsplit = g.rx_floats / stride;
-    if (nsplit > p.ntiles / 2) nsplit = p.ntiles / 2;
-    if (nsplit > 512) nsplit = 512;
-    if (nsplit < 1) nsplit = 1;
-    p.nsplit = (int)nsplit; p.Rx = g.rx; p.rx_stride = stride; p.rx_bias = nloc; p.want_bsum = g.bsum != nullptr;
+    const WgCopies c = m1_wg_copies(g, 1, tgt / (nau * nbu), p.ntiles, PW_COPIES);
+    if (c.rc) return c.rc;
+    const long long nsplit = c.nsplit, stride = c.stride, nloc = c.rx_bias;
+    p.nsplit = (int)nsplit; p.Rx = c.Rx; p.rx_stride = stride; p.rx_bias = nloc; p.want_bsum = g.bsum != nullptr;
     const size_t smem = 2 * (size_t)(2 * (PW_KT / 4) * 1024);
     if (m1_allow_dynamic_lds((const void*)wgrad_pwf_kernel, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_pwf");

@@ -14,7 +14,7 @@
 //   16-lane groups of a transpose read (rows r..r+3 and r+8..r+11) hit disjoint banks.
 // * Few voxel splits per (tap, tile) (~2 blocks per CU in total): float atomics into R.
 #include "common.h"
-#include "gather.h"
+#include "wgrad_fold.h"
 #include "cdna4.h"
 #include <stdlib.h>
 
@@ -225,7 +225,7 @@ static bool tap_plan(const WgradSpec& g, TapP& p) {
     if (!en || g.dtype != M1_BF16) return false;
     if (g.CA < 64 || g.CB < 64 || g.CA % 8 || g.CB % 8) return false;
     if (g.BW % 8 && g.BW > 32) return false;
-    if ((long long)g.N * g.AD * g.AH * g.AW >= (1ll << 31) - (1 << 20) || (long long)g.N * g.BD * g.BH * g.BW >= (1ll << 31) - (1 << 20)) return false;
+    if (!m1_wg_vox32(g)) return false;
     p = TapP{};
     p.A = (const bf16_t*)g.A; p.B = (const bf16_t*)g.B; p.R = g.R; p.bsum = g.bsum; p.bsum_tap = g.bsum_tap;
     p.CA = g.CA; p.CB = g.CB; p.AD = g.AD; p.AH = g.AH; p.AW = g.AW; p.BD = g.BD; p.BH = g.BH; p.BW = g.BW; p.N = g.N;
@@ -233,16 +233,13 @@ static bool tap_plan(const WgradSpec& g, TapP& p) {
     p.kd = g.kd; p.kh = g.kh; p.kw = g.kw; p.sd = g.sd; p.sh = g.sh; p.sw = g.sw; p.pd = g.pd; p.ph = g.ph; p.pw = g.pw;
     // tile = TH rows x KWs columns <= 64 voxels; rows of up to 32 voxels that are no multiple of 8 (W = 20 at the (10,20,20) level)
     // take the whole row: 3 x 20 = 60 voxels + 4 empty slots (89 % of the MFMA work is real, against 62 % for 16 x 4 tiles)
-    p.KWs = g.BW % 32 == 0 ? 32 : (g.BW % 16 == 0 ? 16 : (g.BW % 8 == 0 ? 8 : g.BW));
-    p.TH = 64 / p.KWs;
-    if ((p.TH - 1) * g.sh > 255 || (p.KWs - 1) * g.sw > 255) return false;
-    p.tiles_w = g.BW / p.KWs; p.tiles_h = (g.BH + p.TH - 1) / p.TH;
-    const long long nt = (long long)g.N * g.BD * p.tiles_h * p.tiles_w;
-    if (nt >= (1ll << 30) || nt < 8) return false;
-    p.ntiles = (int)nt;
-    return true;
+    if (!m1_wg_ktiles(g, 64, m1_wg_kws(g.BW, g.BW), 8, p)) return false;
+    return (p.TH - 1) * g.sh <= 255 && (p.KWs - 1) * g.sw <= 255;
 }
 bool m1_tap_wgrad_supported(const WgradSpec& g) { TapP p; return tap_plan(g, p); }
+
+// copies: >= 4 K-tiles each, no ceiling of their own (the rx region is sized for M1_WG_MAX_COPIES)
+static const WgCopyRule TAP_COPIES = {4, 0, 0, WG_SHORT_FALLBACK};
 
 int m1_tap_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     TapP p;
@@ -254,10 +251,14 @@ int m1_tap_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     const int ctiles = aTiles * p.bTiles;
     // round DOWN: 2 blocks per CU x 256 CUs = 512 slots; one block more than that is a second round for its whole XCD
     int rdn = M1_CFG("M1_WG_FLOOR", 1);
-    long long nsplit = rdn ? tgt / ((long long)ctiles * taps) : (tgt + (long long)ctiles * taps - 1) / ((long long)ctiles * taps);
-    if (nsplit > p.ntiles / 4) nsplit = p.ntiles / 4;
-    if (nsplit < 1) nsplit = 1;
+    const long long want = rdn ? tgt / ((long long)ctiles * taps) : (tgt + (long long)ctiles * taps - 1) / ((long long)ctiles * taps);
+    // partial copies + fixed-order fold instead of atomics (compact per-member copies, see wgrad_mfma.hip): bit-reproducible
+    // weight gradients; M1_WG_DET=0 restores the atomic path.  A region too short for two copies: one split.
+    int det = M1_CFG("M1_WG_DET", 1);
+    const WgCopies c = m1_wg_copies(g, taps, want, p.ntiles, TAP_COPIES, det != 0);
+    const long long nsplit = det && !c.Rx ? 1 : c.nsplit;
     p.nsplit = (int)nsplit;
+    p.Rx = c.Rx; p.rx_stride = c.stride; p.rx_bias = c.rx_bias;
     const int stage = 64 * (TA + TB) * 2;
     int S = (76 * 1024) / stage; if (S > 4) S = 4; if (S < 2) S = 2;
     { int fs = M1_CFG("M1_WG_TAP_STAGES", 0); if (fs >= 2) S = fs; }
@@ -269,17 +270,6 @@ int m1_tap_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     else if (TA == 64 && TB == 128) kern = wgrad_tap_kernel<2, 4>;
     else kern = wgrad_tap_kernel<2, 2>;
     if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
-    // partial copies + fixed-order fold instead of atomics (compact per-member copies, see wgrad_mfma.hip): bit-reproducible
-    // weight gradients; M1_WG_DET=0 restores the atomic path
-    int det = M1_CFG("M1_WG_DET", 1);
-    const long long stride = (long long)taps * g.CA * g.CB + g.CB;
-    p.Rx = nullptr; p.rx_stride = stride; p.rx_bias = (long long)taps * g.CA * g.CB;
-    if (det && nsplit >= 2) {
-        long long fit = g.rx ? g.rx_floats / stride : 0;
-        if (fit >= 2) { if (nsplit > fit) nsplit = fit; p.Rx = g.rx; }
-        else nsplit = 1;
-        p.nsplit = (int)nsplit;
-    }
     int xr = M1_CFG("M1_WG_XCD", 1);
     p.ctiles = ctiles; p.taps = taps; p.xcd_total = 0;
     if (xr && taps > 1) {
@@ -291,6 +281,6 @@ int m1_tap_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
         hipLaunchKernelGGL(kern, dim3(ctiles, (unsigned)nsplit, taps), dim3(256), smem, st, p);
     }
     int rc = m1_check_launch(); if (rc) return rc;
-    if (p.Rx) return m1_wg_rx_finish(p.Rx, stride, (int)nsplit, g, p.rx_bias, st);
+    if (p.Rx) return m1_wg_rx_finish(p.Rx, c.stride, (int)nsplit, g, p.rx_bias, st);
     return M1_OK;
 }

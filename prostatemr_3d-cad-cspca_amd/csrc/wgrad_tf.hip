@@ -14,10 +14,10 @@
 // * wave w accumulates the 16x16 tile (w>>1, w&1) of every tap: NT x 4 accumulator registers; the B fragment of a
 //   k-step is read once and reused by all taps.
 // * K-tiles are dealt round-robin to the blocks of a channel tile; every block stores its partial tile into its own copy of the
-//   member's gradient block and a fold (tf_finish_*, queued and run in batches: m1_wgrad_defer) adds the copies in a fixed
+//   member's gradient block and a fold (wgrad_fold.hip: tf_finish_*, queued and run in batches) adds the copies in a fixed
 //   order -- no floating-point atomics.  The equal-width members of a concat share one launch (blockIdx.z = member).
 #include "common.h"
-#include "gather.h"
+#include "wgrad_fold.h"
 #include "cdna4.h"
 #include <stdlib.h>
 
@@ -243,138 +243,6 @@ __global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
 }
 
 
-// R[idx(i)] += sum over the copies of Rx[copy][idx(i)] for the NT x CA x CB block of one concat member (+ its bias sums).
-// A block owns EL consecutive elements; its 256/EL lane rows stride the copies, fold through LDS, and ONE lane adds the
-// total into R -- fixed order, no atomics: the weight gradient of these layers is run-to-run deterministic.
-struct TfFin { float* Rx; long long stride; int ncopies; float* R; int NT, CA, CB; long long RT, RSA; int a_off, b_off;
-               float* bsum; long long rx_bias; int nb; int EL; int bias_serial; };
-// (bodies take the block index / block count of THEIR fold, so that one launch can serve many folds: tf_finish_batch_kernel)
-__device__ __forceinline__ void tf_fold_generic(const TfFin& f, unsigned vb, float* red) {
-    const long long n = (long long)f.NT * f.CA * f.CB;
-    const int e = threadIdx.x % f.EL, y = threadIdx.x / f.EL, YL = 256 / f.EL;
-    const long long i = (long long)vb * f.EL + e;
-    const long long idx = i;                              // the copies are compact: [tap][a][b] of this member, then CB bias sums
-    float* dst = nullptr;
-    if (i < n) {
-        const int b = (int)(i % f.CB); const long long q = i / f.CB; const int a = (int)(q % f.CA), t = (int)(q / f.CA);
-        dst = f.R + (long long)t * f.RT + (long long)(a + f.a_off) * f.RSA + b + f.b_off;
-    } else if (i < n + f.nb) { dst = f.bsum + (i - n) + f.b_off; }
-    float s = 0.f;
-    if (dst) {
-#pragma unroll 8
-        for (int c = y; c < f.ncopies; c += YL) s += f.Rx[(long long)c * f.stride + idx];
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (y == 0 && dst) {
-        for (int q = 1; q < YL; ++q) s += red[q * f.EL + e];
-        *dst += s;
-    }
-}
-__global__ void __launch_bounds__(256) tf_finish_kernel(TfFin f) {
-    __shared__ float red[256];
-    tf_fold_generic(f, blockIdx.x, red);
-}
-
-// Few copies of a large block (deep layers: 2..16 voxel splits of a multi-MB weight block): one thread folds 4 consecutive
-// elements over all copies with 16-byte loads -- bandwidth-bound, where the kernel above (built for hundreds of copies of a
-// small block) spends its time in 55k nearly empty blocks.  Same fixed order of additions.
-__device__ __forceinline__ void tf_fold_vec(const TfFin& f, unsigned vb, unsigned nblk) {
-    const long long n = (long long)f.NT * f.CA * f.CB, n4 = n >> 2;
-    for (long long q = (long long)vb * 256 + threadIdx.x; q < n4; q += (long long)nblk * 256) {
-        const long long i = q << 2;
-        float4 s = *reinterpret_cast<const float4*>(f.Rx + i);
-        for (int c = 1; c < f.ncopies; ++c) {
-            const float4 v = *reinterpret_cast<const float4*>(f.Rx + (long long)c * f.stride + i);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        const int b = (int)(i % f.CB); const long long r = i / f.CB; const int a = (int)(r % f.CA), t = (int)(r / f.CA);
-        float* dst = f.R + (long long)t * f.RT + (long long)(a + f.a_off) * f.RSA + b + f.b_off;
-        dst[0] += s.x; dst[1] += s.y; dst[2] += s.z; dst[3] += s.w;
-    }
-    if (vb == 0)
-        for (int j = threadIdx.x; j < f.nb; j += 256) {
-            float s = 0.f;
-            for (int c = 0; c < f.ncopies; ++c) s += f.Rx[(long long)c * f.stride + n + j];
-            f.bsum[j + f.b_off] += s;
-        }
-}
-__global__ void __launch_bounds__(256) tf_finish_vec_kernel(TfFin f) { tf_fold_vec(f, blockIdx.x, gridDim.x); }
-
-// Many copies (tens to hundreds of voxel splits): a block owns 256 consecutive elements, its 4 waves take every 4th copy with
-// 16-byte loads (1 KB contiguous per wave and copy), fold through LDS in wave order, one store.  Fixed order, coalesced.
-__device__ __forceinline__ void tf_fold_wide(const TfFin& f, unsigned vb, float4 (*red)[64]) {
-    const long long n = (long long)f.NT * f.CA * f.CB;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const long long i = ((long long)vb * 64 + lane) << 2;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < n) {
-#pragma unroll 4
-        for (int c = w; c < f.ncopies; c += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(f.Rx + (long long)c * f.stride + i);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    }
-    red[w][lane] = s;
-    __syncthreads();
-    if (w == 0 && i < n) {
-#pragma unroll
-        for (int q = 1; q < 4; ++q) { const float4 v = red[q][lane]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-        const int b = (int)(i % f.CB); const long long r = i / f.CB; const int a = (int)(r % f.CA), t = (int)(r / f.CA);
-        float* dst = f.R + (long long)t * f.RT + (long long)(a + f.a_off) * f.RSA + b + f.b_off;
-        dst[0] += s.x; dst[1] += s.y; dst[2] += s.z; dst[3] += s.w;
-    }
-    // bias sums (block 0 of the fold): the copies are spread over the lane rows -- 256 / nbp rows stride the copies with four loads in
-    // flight, then fold through LDS in row order.  (Round 6: one thread per bias element used to walk ALL copies, 512 dependent loads
-    // of a single block -- the tail of a batched launch of thousands of blocks, 100-160 us.)
-    if (vb == 0 && f.bias_serial) {                        // (M1_TF_BIAS_SERIAL=1: the round-5 form, for A/B)
-        for (int j = threadIdx.x; j < f.nb; j += 256) {
-            float sb = 0.f;
-            for (int c = 0; c < f.ncopies; ++c) sb += f.Rx[(long long)c * f.stride + n + j];
-            f.bsum[j + f.b_off] += sb;
-        }
-    } else if (vb == 0 && f.nb > 0) {
-        __syncthreads();                                   // (red is reused)
-        float* const rb = reinterpret_cast<float*>(red);   // 256 floats
-        int nbp = 1; while (nbp < f.nb && nbp < 256) nbp <<= 1;
-        const int rows = 256 / nbp, j = threadIdx.x % nbp, r0 = threadIdx.x / nbp;
-        for (int j0 = 0; j0 < f.nb; j0 += nbp) {
-            float sb = 0.f;
-            if (j0 + j < f.nb) {
-#pragma unroll 4
-                for (int c = r0; c < f.ncopies; c += rows) sb += f.Rx[(long long)c * f.stride + n + j0 + j];
-            }
-            rb[threadIdx.x] = sb;
-            __syncthreads();
-            if (r0 == 0 && j0 + j < f.nb) {
-                for (int q = 1; q < rows; ++q) sb += rb[q * nbp + j];
-                f.bsum[j0 + j + f.b_off] += sb;
-            }
-            __syncthreads();
-        }
-    }
-}
-__global__ void __launch_bounds__(256) tf_finish_wide_kernel(TfFin f) {
-    __shared__ float4 red[4][64];
-    tf_fold_wide(f, blockIdx.x, red);
-}
-
-// Many folds in one launch (m1_wgrad_defer / m1_wgrad_fold_pending): a fold of one conv member is 5-10 us of a few dozen blocks;
-// ~130 of them per C3 step, each alone on its stream, were 4 % of the step.  The jobs travel by value in the kernel arguments.
-#define TF_FOLD_MAX 24
-struct TfFoldBatch { int n; int pref[TF_FOLD_MAX + 1]; int mode[TF_FOLD_MAX]; TfFin f[TF_FOLD_MAX]; };
-static_assert(sizeof(TfFoldBatch) <= 3800, "fold batch must fit the kernel argument segment");
-__global__ void __launch_bounds__(256) tf_finish_batch_kernel(TfFoldBatch B) {
-    __shared__ float4 red[4][64];
-    int j = 0;
-    while (j + 1 < B.n && (int)blockIdx.x >= B.pref[j + 1]) ++j;
-    const unsigned vb = blockIdx.x - B.pref[j], nblk = B.pref[j + 1] - B.pref[j];
-    const TfFin& f = B.f[j];
-    if (B.mode[j] == 1) tf_fold_vec(f, vb, nblk);
-    else if (B.mode[j] == 2) tf_fold_wide(f, vb, red);
-    else tf_fold_generic(f, vb, reinterpret_cast<float*>(red));
-}
-
 static inline bool tf_chan_ok(int c) { return c == 8 || c == 16 || (c >= 32 && c % 32 == 0); }
 
 // fills the launch geometry; false = shape outside this kernel (the per-tap kernel of wgrad_mfma.hip takes it)
@@ -384,13 +252,12 @@ static bool tf_plan(const WgradSpec& g, TfP& p) {
     if (!k133 && !k333) return false;
     if (!tf_chan_ok(g.CA) || !tf_chan_ok(g.CB)) return false;
     if (g.BW % 8) return false;
-    if ((long long)g.N * g.AD * g.AH * g.AW >= (1ll << 31) - (1 << 20) || (long long)g.N * g.BD * g.BH * g.BW >= (1ll << 31) - (1 << 20)) return false;
+    if (!m1_wg_vox32(g)) return false;
     p = TfP{};
     p.A = (const bf16_t*)g.A; p.B = (const bf16_t*)g.B; p.R = g.R; p.bsum = g.bsum;
     p.CA = g.CA; p.CB = g.CB; p.AD = g.AD; p.AH = g.AH; p.AW = g.AW; p.BD = g.BD; p.BH = g.BH; p.BW = g.BW; p.N = g.N;
     p.RT = g.RT; p.RSA = g.RSA; p.a_off = g.a_off; p.b_off = g.b_off;
     p.sd = g.sd; p.sh = g.sh; p.sw = g.sw; p.pd = g.pd; p.ph = g.ph; p.pw = g.pw;
-    p.KWs = g.BW % 32 == 0 ? 32 : (g.BW % 16 == 0 ? 16 : 8);
     // K-tile: 128 voxels (4 k-steps per barrier and DMA round trip) for the (1,3,3) kernels and wherever both sides have <= 16
     // channels; 64 for the other (3,3,3) layers, whose 3-slice input tiles would leave one block per CU.  With the members of a
     // concat in one launch (enough blocks per CU) the larger tile pays: 64 -> 32 at (2,20,160,160) 146 -> 112 us, 320 -> 64 at
@@ -398,16 +265,13 @@ static bool tf_plan(const WgradSpec& g, TfP& p) {
     int n4 = M1_CFG("M1_TF_NKS4", 2);
     const int nks = ((n4 && g.CA <= 16 && g.CB <= 16) || (n4 == 2 && g.kd == 1)) ? 4 : 2;
     p.nks = nks;
-    p.TH = nks * (32 / p.KWs);
+    if (!m1_wg_ktiles(g, nks * 32, m1_wg_kws(g.BW, 8), 0, p)) return false;
     p.AHt = (p.TH - 1) * g.sh + g.kh; p.AWt = (p.KWs - 1) * g.sw + g.kw;
     p.spra = (g.CA < 32 ? g.CA : 32) / 8; p.sprb = (g.CB < 32 ? g.CB : 32) / 8;
     const int a_rows = g.kd * p.AHt * p.AWt;
     p.a_slots = (a_rows * p.spra + 255) / 256 * 256; p.b_slots = nks * 32 * p.sprb;
     if (p.a_slots > TF_MAX_AIT * 256 || p.AHt > 255 || p.AWt > 255) return false;
     p.a_bytes = p.a_slots * 16; p.b_bytes = (p.b_slots + 255) / 256 * 256 * 16 + 64;      // (+64: slack for the 32-byte fragment reads of short rows)
-    p.tiles_w = g.BW / p.KWs; p.tiles_h = (g.BH + p.TH - 1) / p.TH;
-    p.ntiles = (long long)g.N * g.BD * p.tiles_h * p.tiles_w;
-    if (p.ntiles >= (1ll << 30)) return false;
     // as many stages as fit ~76 KB (two blocks per CU), at least 3, bounded by the vmcnt range
     const int sb = p.a_bytes + p.b_bytes, npiece = p.a_slots / 256 + (p.b_slots + 255) / 256;
     int S = (76 * 1024) / sb;
@@ -421,79 +285,10 @@ static bool tf_plan(const WgradSpec& g, TfP& p) {
 // 64x64 variant: both sides multiples of 64 channels
 bool m1_tf_wgrad_supported(const WgradSpec& g) { TfP p; return tf_plan(g, p); }
 
-// ---- deferred folds: queued (process-wide, the autograd engine calls the weight gradients from its own thread) and run
-//      in a few batched launches by m1_wgrad_fold_pending ----
-#include <mutex>
-#include <vector>
-struct TfPending { TfFin f; int mode; int blocks; };
-static std::mutex g_fold_mu;
-static std::vector<TfPending> g_fold_pending;
-static int g_fold_defer = 0;
-static int fold_launch_pending_locked(hipStream_t st) {
-    size_t i = 0;
-    while (i < g_fold_pending.size()) {
-        TfFoldBatch B{}; B.pref[0] = 0;
-        while (i < g_fold_pending.size() && B.n < TF_FOLD_MAX) {
-            const TfPending& q = g_fold_pending[i++];
-            B.f[B.n] = q.f; B.mode[B.n] = q.mode; B.pref[B.n + 1] = B.pref[B.n] + q.blocks; ++B.n;
-        }
-        hipLaunchKernelGGL(tf_finish_batch_kernel, dim3((unsigned)B.pref[B.n]), dim3(256), 0, st, B);
-        int rc = m1_check_launch(); if (rc) { g_fold_pending.clear(); return rc; }
-    }
-    g_fold_pending.clear();
-    return M1_OK;
-}
-int m1_fold_defer_set(int on) { std::lock_guard<std::mutex> lk(g_fold_mu); const int was = g_fold_defer; g_fold_defer = on ? 1 : 0; return was; }
-extern "C" int m1_wgrad_defer(int on) { std::lock_guard<std::mutex> lk(g_fold_mu); g_fold_defer = on ? 1 : 0; return M1_OK; }
-int m1_fold_defer_get() { std::lock_guard<std::mutex> lk(g_fold_mu); return g_fold_defer; }
-extern "C" int m1_wgrad_fold_drop(void) { { std::lock_guard<std::mutex> lk(g_fold_mu); g_fold_pending.clear(); } m1_colsum_drop_pending(); return M1_OK; }
-extern "C" int m1_wgrad_fold_pending(void* stream) {
-    if (m1_debug_skip("fold")) return m1_wgrad_fold_drop();
-    {
-        std::lock_guard<std::mutex> lk(g_fold_mu);
-        const int rc = fold_launch_pending_locked((hipStream_t)stream); if (rc) return rc;
-    }
-    return m1_colsum_launch_pending((hipStream_t)stream);        // (the transposed convs' bias gradients queued with the folds)
-}
-
-// shared with the per-tap kernel (wgrad_mfma.hip), which uses the same partial-copy scheme for small weight tensors
-int m1_wg_rx_finish(float* rx, long long stride, int ncopies, const WgradSpec& g, long long nw, hipStream_t st) {
-    TfFin f{rx, stride, ncopies, g.R, g.kd * g.kh * g.kw, g.CA, g.CB, g.RT, g.RSA, g.a_off, g.b_off, g.bsum, nw, g.bsum ? g.CB : 0, 32,
-            M1_CFG("M1_TF_BIAS_SERIAL", 0)};
-    const long long n = (long long)f.NT * f.CA * f.CB + f.nb;
-    int mode = 0; long long blocks;
-    if (ncopies <= 16 && f.CB % 4 == 0 && n >= (1 << 16)) {
-        mode = 1; blocks = (n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096;
-    } else if (f.CB % 4 == 0 && n - f.nb >= (1 << 15)) {            // (n - nb) / 256 >= 128 blocks
-        mode = 2; blocks = (n - f.nb + 255) / 256;
-    } else {
-        while (f.EL > 4 && n / f.EL < 128) f.EL >>= 1;           // small blocks of R: more lane rows per element, more blocks
-        blocks = (n + f.EL - 1) / f.EL;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_fold_mu);
-        if (g_fold_defer) {
-            // Two folds into the same block of R (a parameter used by two passes) must not share a launch (both read-modify-write
-            // R).  The queue may hold folds whose partial copies were written on OTHER streams (SE shortcut / gate branches,
-            // weight-gradient streams) that `st` is not ordered behind, so it is NOT flushed here: this fold runs now, on its own
-            // stream, right behind the kernel that wrote its copies; the queued one follows at m1_wgrad_fold_pending, which the
-            // caller issues on a stream that has joined every stream used since (ops.join_side_streams).
-            bool dup = false;
-            for (const TfPending& q : g_fold_pending)
-                if (q.f.R == f.R && q.f.a_off == f.a_off && q.f.b_off == f.b_off) { dup = true; break; }
-            if (!dup) {
-                g_fold_pending.push_back(TfPending{f, mode, (int)blocks});
-                return M1_OK;
-            }
-        }
-    }
-    if (mode == 1) hipLaunchKernelGGL(tf_finish_vec_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f);
-    else if (mode == 2) hipLaunchKernelGGL(tf_finish_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f);
-    else hipLaunchKernelGGL(tf_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f);
-    return m1_check_launch();
-}
-
-#define TF_MAX_COPY_BYTES (96ll << 20)
+// copies: any K-tile is worth one, no ceiling on their number, 96 MB in all.  (Looks like drift, kept: the rx region is at most
+// 64 MB (M1_WG_RX_MB) and sized for 512 copies, so neither absence nor ceiling binds by default; and where the others would run
+// one split this launcher declines.)
+static const WgCopyRule TF_COPIES = {1, 0, 96ll << 20, WG_SHORT_ERROR};
 static int tf_wgrad_launch(const WgradSpec& g, long long nw, int nb, hipStream_t st, int nmem, const void* const* Am, const int* a_offs, long long rx_mem);
 // `nmem` members of one Conv3D concat at once: member m = (Am[m], a_off a_offs[m]), all with g.CA channels; copies of member m
 // live at g.rx + m * rx_mem (rx_mem >= g.rx_floats of one member)
@@ -513,16 +308,11 @@ static int tf_wgrad_launch(const WgradSpec& g, long long nw, int nb, hipStream_t
     // kernels fill the idle SIMDs: C3 (4 volumes per launch) -2 % with 512, C2 (2 volumes) +1 %
     int tgt_env = M1_CFG("M1_TF_SPLIT", 0);
     const int tgt = tgt_env > 0 ? tgt_env : (p.ntiles >= 24576 ? 512 : 256);
-    long long nsplit = (tgt + ctiles - 1) / ctiles;
-    const long long nloc = (long long)g.kd * g.kh * g.kw * g.CA * g.CB;
-    const long long stride = nloc + g.CB;                      // compact copy of this member's block (+ bias sums)
-    if (nsplit * stride * 4 > TF_MAX_COPY_BYTES) nsplit = TF_MAX_COPY_BYTES / (stride * 4);
-    if (!g.rx || g.rx_floats < stride) return M1_ERR_WORKSPACE;
-    if (nsplit * stride > g.rx_floats) nsplit = g.rx_floats / stride;      // as many copies as the caller's scratch holds
-    if (nsplit > p.ntiles) nsplit = p.ntiles;
-    if (nsplit < 1) return M1_ERR_UNSUPPORTED;
+    const WgCopies c = m1_wg_copies(g, g.kd * g.kh * g.kw, (tgt + ctiles - 1) / ctiles, p.ntiles, TF_COPIES);      // (rounded UP)
+    if (c.rc) return c.rc;
+    const long long nsplit = c.nsplit;
     p.nsplit = (int)nsplit;
-    p.Rx = g.rx; p.rx_stride = stride; p.rx_bias = nloc;
+    p.Rx = c.Rx; p.rx_stride = c.stride; p.rx_bias = c.rx_bias;
     const size_t smem = (size_t)p.stages * (p.a_bytes + p.b_bytes);
     dim3 grid(ctiles, (unsigned)nsplit, 1);
     p.nmem = 1; p.rx_mem = 0;
@@ -544,10 +334,5 @@ static int tf_wgrad_launch(const WgradSpec& g, long long nw, int nb, hipStream_t
     m1_note_kernel("wgrad_tf");
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;
-    if (nmem <= 1) return m1_wg_rx_finish(p.Rx, stride, (int)nsplit, g, nloc, st);
-    for (int m = 0; m < nmem; ++m) {                      // one fold per member (its own block of R; the bias sums ride on member 0)
-        WgradSpec gm = g; gm.a_off = a_offs[m]; if (m) gm.bsum = nullptr;
-        rc = m1_wg_rx_finish(p.Rx + (long long)m * rx_mem, stride, (int)nsplit, gm, nloc, st); if (rc) return rc;
-    }
-    return M1_OK;
+    return m1_wg_fold_members(p.Rx, rx_mem, c.stride, (int)nsplit, g, c.rx_bias, nmem < 1 ? 1 : nmem, a_offs, st);
 }

@@ -12,7 +12,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-@pytest.mark.parametrize("src", ["wgrad_tf.hip", "wgrad_tap.hip", "conv_halo.hip", "conv_pw.hip"])
+@pytest.mark.parametrize("src", ["wgrad_tf.hip", "wgrad_fold.hip", "wgrad_tap.hip", "conv_halo.hip", "conv_pw.hip"])
 def test_hot_kernels_use_no_scratch_memory(src):
     """A run-time index into a by-value kernel-argument array moves the WHOLE argument struct to scratch (private) memory: every
     p.x becomes a scratch load.  It happened once (`p.Am[mem]` in wgrad_tf_kernel: +10 % per C3 step with the feature off) and is

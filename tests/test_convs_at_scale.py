@@ -719,6 +719,66 @@ def test_queued_weight_gradients_equal_direct_and_fp64(dev, pair, monkeypatch):
     ops.drop_deferred(); ops.invalidate_panels(); torch.cuda.empty_cache()
 
 
+# ---- the queue's duplicate rules: the same weight / the same db twice before one fold_pending ----
+QUEUE_TWICE = [("m1_conv3d_wgrad", 4, 5, 10, 10, (128,), 128, (3, 3, 3), (1, 1, 1)),       # the smallest keys of C3_CONV_KEYS
+               ("m1_convT3d_wgrad", 2, 20, 40, 40, (128,), 64, (3, 3, 3), (1, 2, 2))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("q", QUEUE_TWICE, ids=lambda q: f"{q[0][3:]}-{q[1]}x{q[2]}x{q[3]}x{q[4]}-{sum(q[5])}-{q[6]}")
+def test_same_parameter_twice_in_the_queue(dev, q, monkeypatch):
+    """Two backward passes of ONE layer accumulate into the same ``_m1_gsink`` pair before one fold_pending (a parameter used by two
+    passes of a step).  Two read-modify-writes of the same block must not share a batched launch:
+    * fold: the second fold into a queued (R, a_off, b_off) runs at once on its call's stream, the queued one stays (m1_wg_rx_finish);
+    * column sum (transposed conv, db): a second sum into a queued ``out`` is declined and the caller reduces in place (m1_colsum_defer).
+    The kernel log has no entry for folds or column sums, so what was queued is read off the sinks between the calls: with the weight
+    gradients launched in place, a queued fold / sum leaves its sink untouched, one that ran at once has added one gradient; after
+    fold_pending both hold two.  The same through the deferred launches (both calls inside one m1_wgrad_defer window), twice: equal
+    bits run to run.  Not compared bit for bit ACROSS the two orders: which call folds first may change the last bit."""
+    key = _key(*q)
+    name, N, D, H, W, cins, cout, k, s, dts, fl, kern = key
+    dtype, tr = _DT[dts], "convT" in name
+    g = _gen(dev, zlib.crc32(repr(key).encode()) % 10007)
+    xs, w, b, dy = _conv_inputs(dev, dtype, N, (D, H, W), cins, cout, k, s, tr, g)
+    pre_w, pre_b = 2.0 + _randn(tuple(w.shape), g, dev), -1.0 + _randn((cout,), g, dev)
+    ref, mag = ref_conv_with_mag(torch.cat(xs, -1), w, b, s, dy, tr)
+    once = {}
+
+    def run(in_place):
+        wd, bd = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        wd._m1_gsink, bd._m1_gsink = pre_w.clone(), pre_b.clone()
+        with ops.config(M1_T3_MIN_BLOCKS=128), ops.kernel_log() as kl:
+            for i in range(2):
+                y = (ops.conv3d_transpose_same if tr else ops.conv3d_same)([x.to(dtype) for x in xs], wd, bd, k, s)
+                y.backward(dy.to(dtype))
+                if in_place:
+                    torch.cuda.synchronize()
+                    if i == 0:                                # queued: nothing has touched the sinks
+                        assert torch.equal(wd._m1_gsink, pre_w) and torch.equal(bd._m1_gsink, pre_b), key
+                    else:                                     # the duplicates ran at once: ONE gradient in each sink
+                        once["w"], once["b"] = wd._m1_gsink.clone(), bd._m1_gsink.clone()
+            if not in_place:
+                assert len(ops._WGP["jobs"]) == 2 and not [n for n in kl.names if n.startswith("wgrad")], (len(ops._WGP["jobs"]), kl.names)
+            ops.fold_pending()
+            torch.cuda.synchronize()
+        assert not ops._WGP["jobs"] and not ops._FOLD["keep"]
+        assert [n for n in kl.names if n.startswith("wgrad")] == 2 * kern.split("+"), kl.names      # (partial-copy kernels, both times)
+        return wd._m1_gsink, bd._m1_gsink
+    monkeypatch.setitem(ops._BRANCH, "origin", torch.cuda.current_stream())
+    monkeypatch.setitem(ops._FOLD, "async", 0)                # (no fold trigger of its own inside the two backward passes)
+    qa, qb = run(False), run(False)
+    assert torch.equal(qa[0], qb[0]) and torch.equal(qa[1], qb[1]), key
+    monkeypatch.setitem(ops._WGP, "maxvox", 0)                # launched where autograd calls them, folds and column sums still queued
+    da, db_ = run(True), run(True)
+    assert torch.equal(da[0], db_[0]) and torch.equal(da[1], db_[1]), key
+    assert_conv_close(once["w"], pre_w.double() + ref["dw"], mag["dw"] + pre_w.double().abs(), torch.float32, f"dW after the duplicate of {key}", acc=True)
+    assert_conv_close(once["b"], pre_b.double() + ref["db"], mag["db"] + pre_b.double().abs(), torch.float32, f"db after the duplicate of {key}", acc=True)
+    for what, (gw, gb) in (("deferred launches", qa), ("in place", da)):
+        assert_conv_close(gw, pre_w.double() + 2 * ref["dw"], 2 * mag["dw"] + pre_w.double().abs(), torch.float32, f"dW twice ({what}) of {key}", acc=True)
+        assert_conv_close(gb, pre_b.double() + 2 * ref["db"], 2 * mag["db"] + pre_b.double().abs(), torch.float32, f"db twice ({what}) of {key}", acc=True)
+    ops.drop_deferred(); ops.invalidate_panels(); torch.cuda.empty_cache()
+
+
 # ---- packed panels: second call with packed = 1, bit for bit; weights changed behind autograd's back + repack_all against fp64 ----
 PANEL_KEYS = [  # one forward key per kernel family that reads a packed panel (its data gradient runs as well)
     ("m1_conv3d_fwd", 4, 10, 20, 20, (64,), 64, (3, 3, 3), (1, 1, 1)),                     # conv_mfma (K groups)
