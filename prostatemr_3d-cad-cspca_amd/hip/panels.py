@@ -25,6 +25,17 @@ _PANEL_EPOCH = [0]
 _PACK_REG: dict = {}
 _PACK_TABLE = [None]      # device int64 tensor of job-record addresses (rebuilt when the registry changes)
 
+# A repack_all() recorded into a graph reads ITS table through raw addresses at every replay, and re-packs the panels that table
+# lists, no others.  The table therefore stays alive for the life of the process (a few kB per capture), and the weights it covers
+# are frozen (``_m1_frozen`` = the panel epoch of the capture): a geometry such a weight first meets AFTER the capture -- an
+# evaluation at another batch size between replays -- is packed at every call and neither cached nor registered, because no replay
+# would refresh it and the next call would be served a panel of the weights before the update.
+_CAPTURED_TABLES: list = []
+
+
+def _frozen(holder: torch.Tensor) -> bool:
+    return getattr(holder, "_m1_frozen", None) == _PANEL_EPOCH[0]
+
 
 def invalidate_panels() -> None:
     """Call after anything that changes weights through raw pointers without re-packing (e.g. load_weights)."""
@@ -55,6 +66,10 @@ def repack_all() -> None:
         _PACK_TABLE[0] = (torch.tensor(ptrs, dtype=torch.int64).to(ws0.device),
                           torch.tensor(blocks, dtype=torch.int32).to(ws0.device), blocks[-1])
     t, pref, total = _PACK_TABLE[0]
+    if torch.cuda.is_current_stream_capturing() and not any(c is _PACK_TABLE[0] for c in _CAPTURED_TABLES):
+        _CAPTURED_TABLES.append(_PACK_TABLE[0])
+        for (r, _, _, _) in _PACK_REG.values():
+            r()._m1_frozen = _PANEL_EPOCH[0]
     L.check(L.load().m1_pack_batch(_p(t), _p(pref), int(t.numel()), int(total), _stream()), "m1_pack_batch")
 
 
@@ -76,6 +91,8 @@ def _lookup(holder: torch.Tensor, attr: str, weights, prefix, d, transposed: boo
     hit = store[1].get(key)
     if hit is not None:
         return hit, 1
+    if _frozen(holder):                       # a captured repack_all covers this weight, but not this geometry: packed per call
+        return _conv_ws(d, transposed, role, holder.device, zero=True), 0
     ws = _conv_ws(d, transposed, role, holder.device, zero=True)     # zero: unfilled job records must read as empty
     store[1][key] = ws
     out = (C.c_void_p * L.M1_MAX_SRC)()

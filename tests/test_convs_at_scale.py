@@ -846,3 +846,62 @@ def test_packed_panels_second_call_and_repack_after_weight_update(dev, pk, monke
     for i, (g_, r_, m_) in enumerate(zip(dx2, _split(ref["dx"], cins), _split(mag["dx"], cins))):
         assert_conv_close(g_, r_, m_, dtype, f"dx[{i}] after repack_all of {key}")
     ops.drop_deferred(); ops.invalidate_panels(); torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+def test_panel_first_met_after_a_captured_repack_is_not_served_stale(dev, monkeypatch):
+    """A repack_all() recorded into a graph re-packs, at every replay, the panels registered when it was captured.  A geometry the
+    weight first meets AFTER the capture (an evaluation at another batch size between replayed training steps) is not among them: its
+    panel must not be cached across a replayed update.  Geometry A (N = 4) is registered before the capture, geometry B (N = 2) is
+    first met after it; the weights then change through the raw buffer and ONE replay re-packs; both geometries must give the
+    convolution of the new weights against fp64 -- A from its re-packed panel (packed = 1), B packed at the call (packed = 0)."""
+    key = _key("m1_conv3d_fwd", 4, 10, 20, 20, (64,), 64, (3, 3, 3), (1, 1, 1))
+    name, N, D, H, W, cins, cout, k, s, dts, fl, kern = key
+    dtype = _DT[dts]
+    g = _gen(dev, 4242)
+    xs, w, b, dy = _conv_inputs(dev, dtype, N, (D, H, W), cins, cout, k, s, False, g)
+    w2 = _as(0.7 * w + _randn(tuple(w.shape), g, dev, 0.7 / (sum(cins) * k[0] * k[1] * k[2]) ** 0.5), dtype)
+    lib, flags = L.load(), []
+
+    def wrap(*args, _fn=lib.m1_conv3d_fwd):
+        flags.append(int(args[6]))
+        return _fn(*args)
+    monkeypatch.setattr(lib, "m1_conv3d_fwd", wrap)
+    ws = w.clone().requires_grad_(True)                        # a leaf: its panels are cached on it and registered for repack_all
+    xa, xb = xs[0], xs[0][:2].contiguous()
+
+    def fwd(x):
+        del flags[:]
+        with torch.no_grad():
+            y = ops.conv3d_same([x.to(dtype)], ws, b, k, s)
+        torch.cuda.synchronize()
+        return y, sorted(set(flags))
+    panels = PKG.hip.panels
+    try:
+        with ops.config(M1_T3_MIN_BLOCKS=128):
+            ops.invalidate_panels()
+            assert fwd(xa)[1] == [0] and fwd(xa)[1] == [1]
+            ops.repack_all()                                   # eager first: the table the capture records exists
+            table = panels._PACK_TABLE[0]                      # (held here as well: the replay reads it through raw addresses)
+            assert table is not None
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                ops.repack_all()
+            torch.cuda.synchronize()
+            yb0, fb0 = fwd(xb)                                 # first met after the capture
+            assert fb0 == [0]
+            with torch.no_grad():
+                ws.data.copy_(w2)                              # the optimiser's way: no version bump
+            gr.replay()
+            torch.cuda.synchronize()
+            ya, fa = fwd(xa)
+            yb, fb = fwd(xb)
+            still = panels._PACK_TABLE[0] is table             # (read here: leaving ops.config drops every panel)
+        for what, x, y in (("A (registered before the capture)", xa, ya), ("B (first met after the capture)", xb, yb)):
+            ref, mag = ref_conv_with_mag(x, w2, b, s, None, False)
+            assert_conv_close(y, ref["y"], mag["y"], dtype, f"y of geometry {what} after a replayed repack_all")
+        assert fa == [1] and fb == [0], (fa, fb)
+        assert still                                           # the late geometry did not disturb the table the graph reads
+    finally:
+        ops.drop_deferred(); ops.invalidate_panels(); torch.cuda.empty_cache()
