@@ -329,6 +329,26 @@ int m1_mc_accum(const void* logits, int R, int B, long long V, int nc, int dtype
                 void* stream);
 int m1_mc_finish(const float* sum_p, int n_draws, int B, long long V, int nc, float* mean, float* entropy, void* stream);
 
+/* ---- Uncertainty maps of the same draws (csrc/mc.hip): total entropy split into what the draws disagree on and what they agree on ----
+ * Per voxel, N draws p_1..p_N, nats:  expected_entropy = (1/N) sum_r H(p_r), H(p) = -sum_c p_c ln p_c (aleatoric);
+ * mutual_info = entropy - expected_entropy (epistemic, BALD);  variance_c = (1/N) sum_r p_r,c^2 - mean_c^2 (population variance).
+ * m1_mc_accum_u: m1_mc_accum's pass with two more fp32 accumulators, sum_h (B, V) (+)= sum_r H(p_r) and sum_pp (B, V, nc) (+)=
+ * sum_r p_r^2, from the probabilities already in registers (no second read of the logits, no LDS, no atomics).  All three sums
+ * associate alike: the R replicas of a pass in replica order, then old + that.  accumulate == 0 writes all three (no zero fill).
+ * sum_p and samples_out are m1_mc_accum's, bit for bit.  16-byte accesses need every pointer 16-byte aligned (and the replica
+ * stride, as above); element accesses otherwise, with the same bits.
+ * m1_mc_finish_u: mean and entropy as m1_mc_finish (bit for bit for every input without a NaN); expected_entropy (B, V) = sum_h /
+ * n_draws; mutual_info (B, V) and variance (B, V, nc) as defined, values below 0 (rounding) written as +0.  mean may alias sum_p,
+ * expected_entropy sum_h and variance sum_pp: a thread reads its own elements before it writes them.  n_draws == 1 gives
+ * expected_entropy == entropy bit for bit and mutual_info == variance == +0 (p*p and mean*mean are rounded products, never fused).
+ * NaN: a voxel whose softmax is NaN in any draw (a NaN or infinite logit) has NaN in all five maps (the clamp is x < 0 ? 0 : x, and the entropies take every term
+ * that is not <= 0); m1_mc_finish, whose terms are those > 0, writes entropy 0 for such a voxel.  No other voxel is affected.
+ * Arguments are checked as for m1_mc_accum / m1_mc_finish. */
+int m1_mc_accum_u(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, float* sum_h, float* sum_pp,
+                  int accumulate, float* samples_out, void* stream);
+int m1_mc_finish_u(const float* sum_p, const float* sum_h, const float* sum_pp, int n_draws, int B, long long V, int nc, float* mean,
+                   float* entropy, float* expected_entropy, float* mutual_info, float* variance, void* stream);
+
 /* ---- Focal loss on the softmax heads : losses.py:32-49 (FL: renormalise, clip [1e-7, 1-1e-7], -y log p, * y (1-p)^gamma,
  * * alpha, sum over D,H,W,C, mean over the batch; loss(): mean over the y_pred.shape[-1] / nc heads) ----
  * probs (N,V,nheads*nc) fp32 as written by m1_softmax_heads_fwd; y_true (N,V,nc) fp32 or bf16; alpha: nc HOST floats.

@@ -2,6 +2,10 @@
 // --UNET_PROBA_ITER, train_model.py:72, with scipy.stats.entropy) without a per-draw probability tensor.
 //   m1_mc_accum : one forward pass over R replicas of the batch -> sum_p (+)= sum_r softmax(logits_r)        (fp32, (B,V,nc))
 //   m1_mc_finish: mean = sum_p / n, entropy = -sum_c mean_c ln(mean_c)
+//   m1_mc_accum_u / m1_mc_finish_u: the same pass and the same finish with two more accumulators, sum_h (+)= sum_r H(p_r) and
+//   sum_pp (+)= sum_r p_r^2, from the probabilities already in registers -> expected entropy (aleatoric), mutual information
+//   (epistemic, entropy - expected entropy) and the per-class population variance.  The item functions are the ones below with
+//   U = true; U = false is the code of m1_mc_accum / m1_mc_finish, unchanged.
 // Both stream: a thread owns G consecutive voxels (G*nc elements = nc 16-byte vectors of logits) through every replica, so the
 // replica sum lives in registers and nothing is exchanged between threads (no atomics, no LDS).  The voxels behind the last whole
 // group, and everything when a pointer or the replica stride is not 16-byte aligned, take the same code with G = 1.
@@ -47,14 +51,38 @@ __device__ __forceinline__ void mc_st(float* p, const float* o) {
     }
 }
 
-// G voxels starting at element e0 of every replica (rstride elements apart)
-template <typename T, int NC, int G>
+// Which terms -p ln(p) an entropy takes.  U = false is m1_mc_finish's form, p > 0: a term with p == 0 contributes exactly 0 (no
+// 0 * -inf), and so does a NaN.  The *_u entry points take every p that is not <= 0: the same terms for every number, in the same
+// order, and a NaN stays a NaN in the maps instead of reading as "certain".
+template <bool U>
+__device__ __forceinline__ bool mc_term(float p) { return U ? !(p <= 0.f) : (p > 0.f); }
+
+// H(p) = -sum_c p_c ln(p_c) of one draw of one voxel, in mc_finish_item's operation order
+template <int NC>
+__device__ __forceinline__ float mc_draw_entropy(const float* p) {
+    float a = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (mc_term<true>(p[c])) a = a - p[c] * logf(p[c]);
+    return a;
+}
+
+// G voxels starting at element e0 of every replica (rstride elements apart).  U: also sum_h (one value per voxel, from voxel e0 / NC)
+// and sum_pp (laid out as sum_p), every sum in the same association: replicas in replica order, then old + acc.
+template <typename T, int NC, int G, bool U = false>
 __device__ __forceinline__ void mc_accum_item(const T* lg, long long rstride, int R, long long e0, float* sum_p, int accumulate,
-                                              float* samples) {
+                                              float* samples, float* sum_h = nullptr, float* sum_pp = nullptr) {
     constexpr int E = G * NC, LV = sizeof(T) == 2 ? 8 : 4;
     constexpr bool VEC = G > 1;
     float old[E], acc[E];
+    float oldq[U ? E : 1], accq[U ? E : 1], oldh[U ? G : 1], acch[U ? G : 1];
     if (accumulate) mc_ld<E, VEC>(sum_p + e0, old);
+    if constexpr (U) {
+        if (accumulate) {
+            mc_ld<E, VEC>(sum_pp + e0, oldq);
+            mc_ld<G, VEC>(sum_h + e0 / NC, oldh);
+        }
+    }
     for (int r = 0; r < R; ++r) {
         float v[E];
         const T* p = lg + (long long)r * rstride + e0;
@@ -75,12 +103,40 @@ __device__ __forceinline__ void mc_accum_item(const T* lg, long long rstride, in
 #pragma unroll
             for (int k = 0; k < E; ++k) acc[k] = acc[k] + v[k];
         }
+        if constexpr (U) {
+            float h[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) h[g] = mc_draw_entropy<NC>(v + g * NC);
+#pragma unroll
+            for (int k = 0; k < E; ++k) v[k] = v[k] * v[k];                  // (a rounded product: the file is not contracted)
+            if (r == 0) {
+#pragma unroll
+                for (int k = 0; k < E; ++k) accq[k] = v[k];
+#pragma unroll
+                for (int g = 0; g < G; ++g) acch[g] = h[g];
+            } else {
+#pragma unroll
+                for (int k = 0; k < E; ++k) accq[k] = accq[k] + v[k];
+#pragma unroll
+                for (int g = 0; g < G; ++g) acch[g] = acch[g] + h[g];
+            }
+        }
     }
     if (accumulate) {
 #pragma unroll
         for (int k = 0; k < E; ++k) acc[k] = old[k] + acc[k];
     }
     mc_st<E, VEC>(sum_p + e0, acc);
+    if constexpr (U) {
+        if (accumulate) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) accq[k] = oldq[k] + accq[k];
+#pragma unroll
+            for (int g = 0; g < G; ++g) acch[g] = oldh[g] + acch[g];
+        }
+        mc_st<E, VEC>(sum_pp + e0, accq);
+        mc_st<G, VEC>(sum_h + e0 / NC, acch);
+    }
 }
 
 // items [0, ngroups): whole groups of G voxels; items [ngroups, ngroups + ntail): the single voxels behind them.  M = B * V.
@@ -95,12 +151,31 @@ __global__ void __launch_bounds__(256) mc_accum_kernel(const T* __restrict__ lg,
     }
 }
 
-template <int NC, int G>
-__device__ __forceinline__ void mc_finish_item(const float* sum_p, float n, long long v0, float* mean, float* entropy) {
+template <typename T, int NC>
+__global__ void __launch_bounds__(256) mc_accum_u_kernel(const T* __restrict__ lg, int R, long long M, long long ngroups,
+                                                         float* __restrict__ sum_p, float* __restrict__ sum_h,
+                                                         float* __restrict__ sum_pp, int accumulate, float* __restrict__ samples) {
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;
+    const long long items = ngroups + (M - ngroups * G), rstride = M * NC;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        if (i < ngroups) mc_accum_item<T, NC, G, true>(lg, rstride, R, i * (G * NC), sum_p, accumulate, samples, sum_h, sum_pp);
+        else mc_accum_item<T, NC, 1, true>(lg, rstride, R, (ngroups * G + (i - ngroups)) * NC, sum_p, accumulate, samples, sum_h, sum_pp);
+    }
+}
+
+template <int NC, int G, bool U = false>
+__device__ __forceinline__ void mc_finish_item(const float* sum_p, float n, long long v0, float* mean, float* entropy,
+                                               const float* sum_h = nullptr, const float* sum_pp = nullptr, float* expected = nullptr,
+                                               float* mutual = nullptr, float* variance = nullptr) {
     constexpr int E = G * NC;
     constexpr bool VEC = G > 1;
     float m[E], h[G];
+    float q[U ? E : 1], eh[U ? G : 1], mi[U ? G : 1];
     mc_ld<E, VEC>(sum_p + v0 * NC, m);
+    if constexpr (U) {                                  // (everything is read before anything is written: the outputs may alias)
+        mc_ld<E, VEC>(sum_pp + v0 * NC, q);
+        mc_ld<G, VEC>(sum_h + v0, eh);
+    }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         float a = 0.f;
@@ -108,12 +183,30 @@ __device__ __forceinline__ void mc_finish_item(const float* sum_p, float n, long
         for (int c = 0; c < NC; ++c) {
             const float mc = m[g * NC + c] / n;
             m[g * NC + c] = mc;
-            if (mc > 0.f) a = a - mc * logf(mc);        // (mean_c == 0: the term is exactly 0, no 0 * -inf)
+            if (mc_term<U>(mc)) a = a - mc * logf(mc);  // (mean_c == 0: the term is exactly 0, no 0 * -inf)
         }
         h[g] = a;
     }
+    if constexpr (U) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            eh[g] = eh[g] / n;
+            const float d = h[g] - eh[g];
+            mi[g] = d < 0.f ? 0.f : d;                  // (not fmaxf: a NaN stays a NaN)
+        }
+#pragma unroll
+        for (int k = 0; k < E; ++k) {
+            const float d = q[k] / n - m[k] * m[k];     // (population variance; both terms rounded, so n == 1 gives p*p - p*p = +0)
+            q[k] = d < 0.f ? 0.f : d;
+        }
+    }
     mc_st<E, VEC>(mean + v0 * NC, m);
     mc_st<G, VEC>(entropy + v0, h);
+    if constexpr (U) {
+        mc_st<G, VEC>(expected + v0, eh);
+        mc_st<G, VEC>(mutual + v0, mi);
+        mc_st<E, VEC>(variance + v0 * NC, q);
+    }
 }
 
 // (mean may alias sum_p: a thread reads its own elements before it writes them, so no __restrict__ on either)
@@ -125,6 +218,19 @@ __global__ void __launch_bounds__(256) mc_finish_kernel(const float* sum_p, floa
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
         if (i < ngroups) mc_finish_item<NC, G>(sum_p, n, i * G, mean, entropy);
         else mc_finish_item<NC, 1>(sum_p, n, ngroups * G + (i - ngroups), mean, entropy);
+    }
+}
+
+// (mean / expected / variance may alias sum_p / sum_h / sum_pp, so none of the six is __restrict__; entropy and mutual alias nothing)
+template <int NC>
+__global__ void __launch_bounds__(256) mc_finish_u_kernel(const float* sum_p, const float* sum_h, const float* sum_pp, float n,
+                                                          long long M, long long ngroups, float* mean, float* __restrict__ entropy,
+                                                          float* expected, float* __restrict__ mutual, float* variance) {
+    constexpr int G = 4;
+    const long long items = ngroups + (M - ngroups * G);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        if (i < ngroups) mc_finish_item<NC, G, true>(sum_p, n, i * G, mean, entropy, sum_h, sum_pp, expected, mutual, variance);
+        else mc_finish_item<NC, 1, true>(sum_p, n, ngroups * G + (i - ngroups), mean, entropy, sum_h, sum_pp, expected, mutual, variance);
     }
 }
 
@@ -178,6 +284,67 @@ extern "C" int m1_mc_finish(const float* sum_p, int n_draws, int B, long long V,
         case 2: hipLaunchKernelGGL(mc_finish_kernel<2>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
         case 3: hipLaunchKernelGGL(mc_finish_kernel<3>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
         default: hipLaunchKernelGGL(mc_finish_kernel<4>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
+    }
+    return m1_check_launch();
+}
+
+template <typename T>
+static int mc_accum_u_launch(const void* logits, int R, long long M, int nc, float* sum_p, float* sum_h, float* sum_pp, int accumulate,
+                             float* samples, hipStream_t st) {
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;
+    const bool vec = mc_al(logits, 16) && mc_al(sum_p, 16) && mc_al(sum_h, 16) && mc_al(sum_pp, 16) && (!samples || mc_al(samples, 16)) &&
+                     (R == 1 || (M * nc * (long long)sizeof(T)) % 16 == 0);
+    const long long ngroups = vec ? M / G : 0, items = ngroups + (M - ngroups * G);
+    const dim3 grid(m1_grid_for(items, 1)), block(256);
+    const int acc = accumulate != 0;
+    switch (nc) {
+        case 2: hipLaunchKernelGGL((mc_accum_u_kernel<T, 2>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, sum_h, sum_pp, acc, samples); break;
+        case 3: hipLaunchKernelGGL((mc_accum_u_kernel<T, 3>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, sum_h, sum_pp, acc, samples); break;
+        default: hipLaunchKernelGGL((mc_accum_u_kernel<T, 4>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, sum_h, sum_pp, acc, samples); break;
+    }
+    return m1_check_launch();
+}
+
+extern "C" int m1_mc_accum_u(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, float* sum_h, float* sum_pp,
+                             int accumulate, float* samples_out, void* stream) {
+    if (m1_debug_skip("mc_accum")) return M1_OK;
+    if (!logits || !sum_p || !sum_h || !sum_pp || R <= 0 || B <= 0 || V <= 0 || (dtype != M1_F32 && dtype != M1_BF16)) return M1_ERR_BAD_ARG;
+    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
+    if (!mc_al(logits, dtype == M1_BF16 ? 2 : 4) || !mc_al(sum_p, 4) || !mc_al(sum_h, 4) || !mc_al(sum_pp, 4) || !mc_al(samples_out, 4))
+        return M1_ERR_BAD_ARG;
+    const long long M = (long long)B * V;
+    if (M > (1ll << 40) / R) return M1_ERR_BAD_ARG;                   // (element offsets stay far inside 63 bits)
+    const double el = (double)M * nc;
+    M1ProfScope ps("mc_accum_u", 0.0, el * R * (dtype == M1_BF16 ? 2 : 4) + (2.0 * el + (double)M) * 4 * (accumulate ? 2 : 1) +
+                   (samples_out ? el * R * 4 : 0.0), (hipStream_t)stream);
+    return dtype == M1_BF16 ? mc_accum_u_launch<bf16_t>(logits, R, M, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, (hipStream_t)stream)
+                            : mc_accum_u_launch<float>(logits, R, M, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, (hipStream_t)stream);
+}
+
+extern "C" int m1_mc_finish_u(const float* sum_p, const float* sum_h, const float* sum_pp, int n_draws, int B, long long V, int nc,
+                              float* mean, float* entropy, float* expected_entropy, float* mutual_info, float* variance, void* stream) {
+    if (m1_debug_skip("mc_finish")) return M1_OK;
+    if (!sum_p || !sum_h || !sum_pp || !mean || !entropy || !expected_entropy || !mutual_info || !variance || n_draws <= 0 || B <= 0 ||
+        V <= 0)
+        return M1_ERR_BAD_ARG;
+    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
+    const void* ptrs[8] = {sum_p, sum_h, sum_pp, mean, entropy, expected_entropy, mutual_info, variance};
+    bool vec = true;
+    for (const void* p : ptrs) {
+        if (!mc_al(p, 4)) return M1_ERR_BAD_ARG;
+        vec = vec && mc_al(p, 16);
+    }
+    const long long M = (long long)B * V;
+    if (M > (1ll << 40)) return M1_ERR_BAD_ARG;
+    const long long ngroups = vec ? M / 4 : 0, items = ngroups + (M - ngroups * 4);
+    const dim3 grid(m1_grid_for(items, 1)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    M1ProfScope ps("mc_finish_u", 0.0, (double)M * ((2.0 * nc + 1.0) + (2.0 * nc + 3.0)) * 4, st);      // (read sums, write five maps)
+    const float n = (float)n_draws;
+    switch (nc) {
+        case 2: hipLaunchKernelGGL(mc_finish_u_kernel<2>, grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected_entropy, mutual_info, variance); break;
+        case 3: hipLaunchKernelGGL(mc_finish_u_kernel<3>, grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected_entropy, mutual_info, variance); break;
+        default: hipLaunchKernelGGL(mc_finish_u_kernel<4>, grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected_entropy, mutual_info, variance); break;
     }
     return m1_check_launch();
 }

@@ -894,6 +894,64 @@ def mc_finish(sum_p: torch.Tensor, n: int):
     return sum_p, ent
 
 
+def mc_accum_u(logits: torch.Tensor, R: int, acc=None, samples: bool = False):
+    """``mc_accum`` with the accumulators of the uncertainty maps (m1_mc_accum_u): ``acc`` = (sum_p (B, D, H, W, nc), sum_h (B, D, H, W),
+    sum_pp (B, D, H, W, nc)), all fp32; sum_h (+)= sum_r H(softmax(logits_r)), sum_pp (+)= sum_r softmax(logits_r)^2.  ``acc=None`` starts
+    the triple -- written, not added to, so no zero fill; a given triple is added to in place.  Returns the triple, or ``(triple,
+    per-draw probabilities)`` with ``samples`` as in ``mc_accum``.  sum_p and the samples are ``mc_accum``'s, bit for bit."""
+    _no_grad_only("mc_accum_u")
+    _req(logits)
+    R = int(R)
+    if logits.dim() < 3 or R < 1 or int(logits.shape[0]) % R:
+        raise RuntimeError(f"mc_accum_u: logits {tuple(logits.shape)} do not hold {R} replicas of a batch")
+    B, nc = int(logits.shape[0]) // R, int(logits.shape[-1])
+    shape = (B, *logits.shape[1:])
+    V = logits.numel() // (R * B * nc)
+    if acc is None:
+        add = 0
+        acc = tuple(torch.empty(s, dtype=torch.float32, device=logits.device) for s in (shape, shape[:-1], shape))
+    else:
+        add, acc = 1, tuple(acc)
+        if len(acc) != 3:
+            raise RuntimeError(f"mc_accum_u: acc must be (sum_p, sum_h, sum_pp), got {len(acc)} tensors")
+        _req(*acc)
+        for t, s, what in zip(acc, (shape, shape[:-1], shape), ("sum_p", "sum_h", "sum_pp")):
+            if t.dtype != torch.float32 or tuple(t.shape) != tuple(s):
+                raise RuntimeError(f"mc_accum_u: {what} must be fp32 {tuple(s)}, got {t.dtype} {tuple(t.shape)}")
+    draws = None
+    if isinstance(samples, torch.Tensor):
+        draws = samples
+        _req(draws)
+        if draws.dtype != torch.float32 or tuple(draws.shape) != (R, *shape):
+            raise RuntimeError(f"mc_accum_u: samples must be fp32 {(R, *shape)}, got {draws.dtype} {tuple(draws.shape)}")
+    elif samples:
+        draws = torch.empty((R, *shape), dtype=torch.float32, device=logits.device)
+    L.check(L.load().m1_mc_accum_u(_p(logits), R, B, V, nc, _dt(logits), _p(acc[0]), _p(acc[1]), _p(acc[2]), add, _p(draws), _stream()),
+            "m1_mc_accum_u")
+    return acc if draws is None else (acc, draws)
+
+
+def mc_finish_u(acc, n: int):
+    """The five maps of ``n`` accumulated draws (m1_mc_finish_u) from ``acc`` = mc_accum_u's triple: {"mean" (over sum_p), "entropy",
+    "expected_entropy" = sum_h / n (over sum_h), "mutual_info" = max(entropy - expected_entropy, 0), "variance" = max(sum_pp / n -
+    mean^2, 0) (over sum_pp)}, nats, fp32.  mean and entropy are ``mc_finish``'s, bit for bit, unless a draw held a NaN: then every map
+    of that voxel is NaN here, where ``mc_finish``'s entropy reads 0."""
+    _no_grad_only("mc_finish_u")
+    acc = tuple(acc)
+    if len(acc) != 3:
+        raise RuntimeError(f"mc_finish_u: acc must be (sum_p, sum_h, sum_pp), got {len(acc)} tensors")
+    sum_p, sum_h, sum_pp = acc
+    _req(sum_p, sum_h, sum_pp)
+    if (any(t.dtype != torch.float32 for t in acc) or sum_p.dim() < 2 or int(n) < 1 or sum_pp.shape != sum_p.shape
+            or tuple(sum_h.shape) != tuple(sum_p.shape[:-1])):
+        raise RuntimeError("mc_finish_u: acc must be the fp32 accumulators of mc_accum_u and n >= 1")
+    B, nc = int(sum_p.shape[0]), int(sum_p.shape[-1])
+    ent, mi = (torch.empty(sum_h.shape, dtype=torch.float32, device=sum_p.device) for _ in range(2))
+    L.check(L.load().m1_mc_finish_u(_p(sum_p), _p(sum_h), _p(sum_pp), int(n), B, sum_p.numel() // (B * nc), nc, _p(sum_p), _p(ent),
+                                    _p(sum_h), _p(mi), _p(sum_pp), _stream()), "m1_mc_finish_u")
+    return {"mean": sum_p, "entropy": ent, "expected_entropy": sum_h, "mutual_info": mi, "variance": sum_pp}
+
+
 # ---------------------------------------------------------------------------------------------------------
 # Per-case scoring of a validation batch (validate.hip; validation.validate)
 # ---------------------------------------------------------------------------------------------------------

@@ -925,7 +925,44 @@ class M1(LoadableModel):
             def predict(self, x, **kw):
                 return self.forward(x, **kw)
 
-            def predict_mc(self, x, n_draws, draws_per_pass=1, return_samples=False, eps_p=None):
+            def _mc_passes(self, x, n, R, uncertainty=False, eps_p=None, carry=None, total=0, first=0, advance=True):
+                """``n // R`` passes of ``R`` replicas each, folded into the accumulators ``carry`` = (sums, draws) of an earlier call
+                (another model's, see ``Ensemble``) or into fresh ones; returns (sums, draws), one entry per stage.  sums[j] is
+                ops.mc_accum's sum_p, or ops.mc_accum_u's triple with ``uncertainty``.  ``total`` > 0 asks for the per-draw
+                probabilities: draws[j] is (total, B, D, H, W, nc), and this call fills [first, first + n).  The {seed, step} state
+                advances once per pass unless ``advance`` is False."""
+                prob = outer.references.probabilistic
+                casc = outer.references.cascaded != False  # noqa: E712
+                rep = (lambda t: t.repeat(R, 1, 1, 1, 1)) if R > 1 else (lambda t: t)
+                accum = ops.mc_accum_u if uncertainty else ops.mc_accum
+                sums, draws = carry if carry is not None else (None, None)
+                with torch.no_grad():
+                    if casc:
+                        x1, x2 = outer._cascade_inputs(x)
+                        xin = (rep(outer._prep(x1, channels=outer.input_channels)), rep(outer._prep(x2, channels=outer.input_channels)))
+                    else:
+                        xin = rep(outer._prep(x))
+                    for k in range(n // R):
+                        if casc:
+                            outer._forward_cascaded(xin, eps_p=eps_p, with_infer=prob)
+                            outs = outer._last_cascade
+                        else:
+                            outs = (outer.m1_model(xin, train_outputs=False, eps_p=eps_p) if prob else outer.m1_model(xin),)
+                        logits = [o['prob_infer_conv'] if prob else o['logits'] for o in outs]
+                        if sums is None:
+                            sums = [None] * len(logits)
+                        if total and draws is None:
+                            draws = [torch.empty((total, int(l.shape[0]) // R, *l.shape[1:]), dtype=torch.float32, device=l.device)
+                                     for l in logits]
+                        for j, l in enumerate(logits):
+                            lo = first + k * R
+                            r = accum(l, R, sums[j], samples=draws[j][lo:lo + R] if total else False)
+                            sums[j] = r[0] if total else r
+                        if advance:
+                            outer.advance_rng()
+                return sums, draws
+
+            def predict_mc(self, x, n_draws, draws_per_pass=1, return_samples=False, eps_p=None, uncertainty=False):
                 """Monte-Carlo inference (the reference's --UNET_PROBA_ITER, train_model.py:72): ``n_draws`` hypotheses of ``predict`` --
                 fresh dropout masks and, for the probabilistic model, fresh z ~ P at every level -- folded into
                 {"mean": (B,D,H,W,nc) fp32, "entropy": (B,D,H,W) fp32 in nats (scipy.stats.entropy of the mean)
@@ -935,75 +972,34 @@ class M1(LoadableModel):
                 draws for itself.  The head's raw logits go to ops.mc_accum, which keeps only the running sum of the probabilities;
                 ops.mc_finish divides and takes the entropy.  The {seed, step} state advances once per pass: the first draw is what
                 ``predict(x)`` returns at the current state, and the call leaves the state at step + n_draws / draws_per_pass.
-                ``eps_p`` (injected draws, as in ``forward``) only with n_draws == 1: every draw would be the same."""
-                n, R = int(n_draws), int(draws_per_pass)
-                if n < 1 or R < 1 or n % R:
-                    raise ValueError(f"predict_mc: n_draws >= 1 and draws_per_pass dividing it expected, got {n_draws} / {draws_per_pass}")
+                ``eps_p`` (injected draws, as in ``forward``) only with n_draws == 1: every draw would be the same.
+                ``uncertainty``: the passes go through ops.mc_accum_u / ops.mc_finish_u and the result gains, per voxel and in nats,
+                "expected_entropy" (B,D,H,W) = the mean of the draws' own entropies (what every draw agrees is ambiguous),
+                "mutual_info" (B,D,H,W) = entropy - expected_entropy >= 0 (what the draws disagree on) and "variance" (B,D,H,W,nc),
+                the population variance of the draws per class.  mean, entropy, samples and the state after the call are those of
+                the call without it; one draw gives mutual_info = variance = +0."""
+                n, R = _mc_counts(n_draws, draws_per_pass)
                 if eps_p is not None and n > 1:
                     raise ValueError("predict_mc: injected eps_p with n_draws > 1 would repeat one draw n_draws times")
-                prob = outer.references.probabilistic
-                casc = outer.references.cascaded != False  # noqa: E712
-                rep = (lambda t: t.repeat(R, 1, 1, 1, 1)) if R > 1 else (lambda t: t)
-                with torch.no_grad():
-                    if casc:
-                        x1, x2 = outer._cascade_inputs(x)
-                        xin = (rep(outer._prep(x1, channels=outer.input_channels)), rep(outer._prep(x2, channels=outer.input_channels)))
-                    else:
-                        xin = rep(outer._prep(x))
-                    sums = draws = None
-                    for k in range(n // R):
-                        if casc:
-                            outer._forward_cascaded(xin, eps_p=eps_p, with_infer=prob)
-                            outs = outer._last_cascade
-                        else:
-                            outs = (outer.m1_model(xin, train_outputs=False, eps_p=eps_p) if prob else outer.m1_model(xin),)
-                        logits = [o['prob_infer_conv'] if prob else o['logits'] for o in outs]
-                        if k == 0:
-                            sums = [None] * len(logits)
-                            if return_samples:
-                                draws = [torch.empty((n, int(l.shape[0]) // R, *l.shape[1:]), dtype=torch.float32, device=l.device)
-                                         for l in logits]
-                        for j, l in enumerate(logits):
-                            r = ops.mc_accum(l, R, sums[j], samples=draws[j][k * R:(k + 1) * R] if return_samples else False)
-                            sums[j] = r[0] if return_samples else r
-                        outer.advance_rng()
-                    res = []
-                    for j, s in enumerate(sums):
-                        mean, ent = ops.mc_finish(s, n)
-                        res.append({"mean": mean, "entropy": ent, **({"samples": draws[j]} if return_samples else {})})
-                return res if casc else res[0]
+                sums, draws = self._mc_passes(x, n, R, uncertainty, eps_p, total=n if return_samples else 0)
+                res = _mc_results(sums, draws, n, uncertainty)
+                return res if outer.references.cascaded != False else res[0]  # noqa: E712
 
             def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
-                             **prepare_kw):
+                             uncertainty=False, **prepare_kw):
                 """From a raw scan to a prediction on the scan's own grid: preprocess.prepare_scan to the model's input size, ``predict``
                 (n_draws == 1) or ``predict_mc``, then preprocess.restore of the result.  ``raw``: (B,d,h,w,C) fp32 / int16 on the
                 device at ``spacing`` (cascaded: the pair or dict of the two stages' scans, both on one grid); ``prepare_kw`` goes to
                 prepare_scan (pad_mode, constant_values, dtype, default_value).  Returns {"mean": (B,d,h,w,nsel) fp32, the channels
                 ``channels`` of the restored softmax [, "entropy": (B,d,h,w) with n_draws > 1] [, "labels": (B,d,h,w) uint8, the argmax
                 of the restored softmax, with ``labels``], "network": what predict / predict_mc returned on the network's grid}; a
-                cascaded model returns [stage 1, stage 2] of these.  Host composition only."""
-                from .. import preprocess as PP
+                cascaded model returns [stage 1, stage 2] of these.  ``uncertainty``: the call goes through ``predict_mc(...,
+                uncertainty=True)`` even with one draw, and the result gains "expected_entropy" and "mutual_info" (B,d,h,w), restored
+                as the entropy is, and "variance" (B,d,h,w,nsel), restored with the channel selection of the mean.  Host composition
+                only (``_predict_scan``, shared with ``Ensemble``)."""
                 casc = outer.references.cascaded != False  # noqa: E712
-                raws = list(outer._cascade_inputs(raw)) if casc else [raw]
-                shape = tuple(int(v) for v in raws[0].shape[1:4])
-                if any(tuple(int(v) for v in r.shape[1:4]) != shape for r in raws):
-                    raise ValueError(f"predict_scan: both stages' scans must share one grid, got {[tuple(r.shape) for r in raws]}")
-                xs = [PP.prepare_scan(r, spacing, out_spacing, outer.input_spatial_dims, percentile=percentile, **prepare_kw)[0]
-                      for r in raws]
-                x = xs if casc else xs[0]
-                net = self.predict(x) if int(n_draws) == 1 else self.predict_mc(x, n_draws, draws_per_pass)
-                res = []
-                for o in (net if casc else [net]):
-                    mean = o["mean"] if isinstance(o, dict) else o
-                    r = PP.restore(mean.contiguous(), shape, spacing, out_spacing, order=1, channels=channels, labels=labels)
-                    d = {"mean": r[0] if labels else r}
-                    if isinstance(o, dict):
-                        d["entropy"] = PP.restore(o["entropy"].unsqueeze(-1), shape, spacing, out_spacing, order=1)[..., 0]
-                    if labels:
-                        d["labels"] = r[1]
-                    d["network"] = o
-                    res.append(d)
-                return res if casc else res[0]
+                return _predict_scan(self, outer.input_spatial_dims, outer._cascade_inputs if casc else None, raw, spacing, out_spacing,
+                                     n_draws, draws_per_pass, percentile, channels, labels, uncertainty, prepare_kw)
         return _Detect()
 
     # ---- networks.py:209-223 ---------------------------------------------------------------------------------
@@ -1078,3 +1074,140 @@ class M1(LoadableModel):
         if getattr(opt, "guarded", False):          # (the loss above already synchronised)
             logs["grad_norm"], logs["skipped"] = opt.grad_norm, opt.skipped_steps
         return logs
+
+
+# ============================================================================================================
+# Monte-Carlo inference: what the detect model and an ensemble of detect models share (host composition only)
+# ============================================================================================================
+def _mc_counts(n_draws, draws_per_pass):
+    n, R = int(n_draws), int(draws_per_pass)
+    if n < 1 or R < 1 or n % R:
+        raise ValueError(f"predict_mc: n_draws >= 1 and draws_per_pass dividing it expected, got {n_draws} / {draws_per_pass}")
+    return n, R
+
+
+def _mc_results(sums, draws, n, uncertainty):
+    """The accumulators of ``_mc_passes`` after ``n`` draws in all -> one result dict per stage."""
+    res = []
+    with torch.no_grad():
+        for j, s in enumerate(sums):
+            if uncertainty:
+                d = ops.mc_finish_u(s, n)
+            else:
+                mean, ent = ops.mc_finish(s, n)
+                d = {"mean": mean, "entropy": ent}
+            if draws is not None:
+                d["samples"] = draws[j]
+            res.append(d)
+    return res
+
+
+def _predict_scan(predictor, dims, cascade_inputs, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile, channels, labels,
+                  uncertainty, prepare_kw):
+    """``predict_scan`` of anything with ``predict`` / ``predict_mc``: prepare_scan to the network's grid ``dims``, the prediction,
+    preprocess.restore of every map.  ``cascade_inputs``: the cascaded model's splitter of ``raw`` into its two scans, else None."""
+    from .. import preprocess as PP
+    casc = cascade_inputs is not None
+    raws = list(cascade_inputs(raw)) if casc else [raw]
+    shape = tuple(int(v) for v in raws[0].shape[1:4])
+    if any(tuple(int(v) for v in r.shape[1:4]) != shape for r in raws):
+        raise ValueError(f"predict_scan: both stages' scans must share one grid, got {[tuple(r.shape) for r in raws]}")
+    xs = [PP.prepare_scan(r, spacing, out_spacing, dims, percentile=percentile, **prepare_kw)[0] for r in raws]
+    x = xs if casc else xs[0]
+    if uncertainty:
+        net = predictor.predict_mc(x, n_draws, draws_per_pass, uncertainty=True)
+    else:
+        net = predictor.predict(x) if int(n_draws) == 1 else predictor.predict_mc(x, n_draws, draws_per_pass)
+    res = []
+    for o in (net if casc else [net]):
+        mean = o["mean"] if isinstance(o, dict) else o
+        r = PP.restore(mean.contiguous(), shape, spacing, out_spacing, order=1, channels=channels, labels=labels)
+        d = {"mean": r[0] if labels else r}
+        if isinstance(o, dict):
+            for k in ("entropy", "expected_entropy", "mutual_info"):
+                if k in o:
+                    d[k] = PP.restore(o[k].unsqueeze(-1), shape, spacing, out_spacing, order=1)[..., 0]
+            if "variance" in o:
+                d["variance"] = PP.restore(o["variance"].contiguous(), shape, spacing, out_spacing, order=1, channels=channels)
+        if labels:
+            d["labels"] = r[1]
+        d["network"] = o
+        res.append(d)
+    return res if casc else res[0]
+
+
+class Ensemble:
+    """Several non-cascaded ``M1`` models -- the trainer's one model per fold (--FOLDS 0 1 2 3 4) -- as one predictor.  An ensemble is
+    more draws into the same accumulators: every member's passes are folded by ops.mc_accum[_u] into the sums the previous member
+    left, in list order, and finished once with N = members * n_draws.  With ``uncertainty`` the between-draw term (mutual_info,
+    variance) therefore also carries the disagreement between the folds.
+    Each member draws from its own {seed, step} state, which advances exactly as that member's own ``predict_mc`` call would;
+    ``seed`` gives member i ``seed_dropout(seed + i)``.
+    ``Ensemble([m])`` equals ``m.get_detect_model()`` bit for bit from the same state.  The order of the members is the order of the
+    summation: ensembles of the same members in another order agree to rounding (the tests' bound), not to the bit."""
+
+    def __init__(self, models, seed=None):
+        models = list(models)
+        if not models:
+            raise ValueError("Ensemble: at least one model expected")
+        for i, m in enumerate(models):
+            if not isinstance(m, M1):
+                raise ValueError(f"Ensemble: member {i} is a {type(m).__name__}, not an M1")
+            if m.references.cascaded != False:  # noqa: E712
+                raise NotImplementedError(f"Ensemble: member {i} is a cascaded model ('{m.references.cascaded}'); only single-stage "
+                                          "members are supported")
+        for what in ("num_classes", "input_spatial_dims", "input_channels"):
+            vals = [getattr(m, what) for m in models]
+            if any(v != vals[0] for v in vals):
+                raise ValueError(f"Ensemble: members disagree in {what}: {vals}")
+        self.models = models
+        self.detectors = [m.get_detect_model() for m in models]
+        self.num_classes, self.input_spatial_dims = models[0].num_classes, models[0].input_spatial_dims
+        self.input_channels = models[0].input_channels
+        if seed is not None:
+            for i, m in enumerate(models):
+                m.seed_dropout(int(seed) + i)
+
+    @classmethod
+    def load(cls, paths, device, compute_dtype=None, seed=None):
+        """One member per entry of ``paths`` through ``M1.load``: a checkpoint file (model_weights_NNN.npz), or a fold directory, of
+        which the checkpoint with the highest number is taken.  Members are moved to ``device`` and put in eval mode."""
+        import glob
+        models = []
+        for p in paths:
+            if _os.path.isdir(p):
+                found = sorted(glob.glob(_os.path.join(p, "model_weights_*.npz")))
+                if not found:
+                    raise FileNotFoundError(f"Ensemble.load: no model_weights_*.npz in {p}")
+                p = found[-1]
+            m = M1.load(p).to(device)
+            if compute_dtype is not None:
+                m.set_compute_dtype(compute_dtype)
+            m.eval()
+            models.append(m)
+        return cls(models, seed=seed)
+
+    def _fold(self, x, n, R, uncertainty, samples, advance=True):
+        carry, total = None, len(self.detectors) * n if samples else 0
+        for i, dm in enumerate(self.detectors):
+            carry = dm._mc_passes(x, n, R, uncertainty, carry=carry, total=total, first=i * n, advance=advance)
+        return carry
+
+    def predict(self, x):
+        """(B,D,H,W,nc) fp32: the mean of the members' ``predict(x)``, one draw each at the member's current state (which does not
+        move, as in ``predict``)."""
+        sums, _ = self._fold(x, 1, 1, False, False, advance=False)
+        return _mc_results(sums, None, len(self.detectors), False)[0]["mean"]
+
+    def predict_mc(self, x, n_draws, draws_per_pass=1, uncertainty=False, return_samples=False):
+        """``predict_mc`` of the detect model over N = members * n_draws draws, ``n_draws`` per member; "samples" (N,B,D,H,W,nc) are
+        member-major (member i's draws at [i * n_draws, (i + 1) * n_draws))."""
+        n, R = _mc_counts(n_draws, draws_per_pass)
+        sums, draws = self._fold(x, n, R, uncertainty, return_samples)
+        return _mc_results(sums, draws, len(self.detectors) * n, uncertainty)[0]
+
+    def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
+                     uncertainty=False, **prepare_kw):
+        """``predict_scan`` of the detect model, with this ensemble's ``predict`` / ``predict_mc`` in the middle."""
+        return _predict_scan(self, self.input_spatial_dims, None, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile,
+                             channels, labels, uncertainty, prepare_kw)
