@@ -349,6 +349,21 @@ int m1_mc_accum_u(const void* logits, int R, int B, long long V, int nc, int dty
 int m1_mc_finish_u(const float* sum_p, const float* sum_h, const float* sum_pp, int n_draws, int B, long long V, int nc, float* mean,
                    float* entropy, float* expected_entropy, float* mutual_info, float* variance, void* stream);
 
+/* ---- Test-time augmentation by mirroring (csrc/mc.hip): a mirrored view is one more draw, un-mirrored while it is summed ----
+ * A view is a 3-bit mask: bit 0 mirrors W, bit 1 mirrors H, bit 2 mirrors D.  The masks of the R <= 16 replicas of a pass travel by
+ * value in `flips`, replica r in bits [3r, 3r + 3): no device table, no memcpy node, so the calls can be captured.
+ * m1_mc_accum_v: logits (R*B, D, H, W, nc) bf16 / fp32, replica-major; the accumulators as for m1_mc_accum[_u] with V = D*H*W.  Output
+ * voxel (b, d, h, w) takes replica r's voxel (b, d', h', w'), x' = extent - 1 - x where the bit of x is set in mask r.  sum_h ==
+ * sum_pp == NULL: m1_mc_accum; both given: m1_mc_accum_u; exactly one: M1_ERR_BAD_ARG.  samples_out (R, B, D, H, W, nc) receives the
+ * UN-mirrored per-draw probabilities.  The result equals m1_mc_accum[_u] on logits un-mirrored beforehand, bit for bit, in every
+ * accumulator and in the samples; with flips == 0 it equals that entry point on the same arguments.  16-byte accesses need W to be
+ * a multiple of the group (4 voxels fp32, 8 bf16) besides the alignment m1_mc_accum asks for; element accesses otherwise, same bits.
+ * R > 16: M1_ERR_UNSUPPORTED; a bit of flips at or above 3R: M1_ERR_BAD_ARG; everything else as m1_mc_accum.
+ * m1_tta_views: out (R*B, D, H, W, C), replica r = x (B, D, H, W, C) mirrored by mask r; a copy, bf16 / fp32, any C >= 1. */
+int m1_mc_accum_v(const void* logits, int R, int B, int D, int H, int W, int nc, int dtype, unsigned long long flips, float* sum_p,
+                  float* sum_h, float* sum_pp, int accumulate, float* samples_out, void* stream);
+int m1_tta_views(const void* x, int B, int D, int H, int W, int C, int dtype, int R, unsigned long long flips, void* out, void* stream);
+
 /* ---- Focal loss on the softmax heads : losses.py:32-49 (FL: renormalise, clip [1e-7, 1-1e-7], -y log p, * y (1-p)^gamma,
  * * alpha, sum over D,H,W,C, mean over the batch; loss(): mean over the y_pred.shape[-1] / nc heads) ----
  * probs (N,V,nheads*nc) fp32 as written by m1_softmax_heads_fwd; y_true (N,V,nc) fp32 or bf16; alpha: nc HOST floats.

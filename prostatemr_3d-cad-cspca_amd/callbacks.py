@@ -75,16 +75,17 @@ class Validate(Callback):
     keeps the ``val_*`` keys in its history), are appended to ``self.history`` as ``{"epoch": e+1, ...}``, and on rank 0 become one
     row ``epoch, <metrics...>`` of ``<metrics_dir>/validation.csv`` -- header once, a resumed run appends; CSV and not the
     reference's ``.xlsx``, because openpyxl may be absent.  ``validate_kw`` goes to ``validation.validate`` (draws_per_pass, alpha,
-    gamma, spacing).  Under data parallelism every rank holds this callback: ``validate`` is collective."""
+    gamma, spacing); ``tta`` (mirrored views, ``unets.networks.tta_views``) goes there too when it is given.  Under data parallelism every rank holds this callback: ``validate`` is collective."""
 
     def __init__(self, model, valid_data, steps, every_n_epochs, min_epoch, n_draws, train_obj, metrics_dir=None, init_epoch=0,
-                 rank: int = 0, world: int = 1, **validate_kw):
+                 rank: int = 0, world: int = 1, tta=None, **validate_kw):
         self.model = model
         self.data = valid_data
         self.steps = int(steps)
         self.N = max(int(every_n_epochs), 1)
         self.M = int(min_epoch)
         self.n_draws = int(n_draws)
+        self.tta = tta
         self.train_obj = train_obj
         self.D = metrics_dir
         self.epoch = int(init_epoch)
@@ -94,8 +95,9 @@ class Validate(Callback):
 
     def _validate(self) -> dict:
         from . import validation
+        kw = self.kw if self.tta is None else dict(self.kw, tta=self.tta)
         return validation.validate(self.model, self.data, self.steps, self.train_obj, n_draws=self.n_draws, rank=self.rank,
-                                   world=self.world, **self.kw)
+                                   world=self.world, **kw)
 
     def _append_row(self, epoch: int, metrics: dict) -> None:
         os.makedirs(self.D, exist_ok=True)

@@ -348,3 +348,245 @@ extern "C" int m1_mc_finish_u(const float* sum_p, const float* sum_h, const floa
     }
     return m1_check_launch();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Test-time augmentation by mirroring: a view is a replica whose logits are read at mirrored coordinates.
+//   m1_mc_accum_v: m1_mc_accum / m1_mc_accum_u over (B, D, H, W) with one 3-bit mirror mask per replica (bit 0: W, bit 1: H, bit 2:
+//   D; replica r owns bits [3r, 3r + 3) of `flips`, passed by value: no device table, no memcpy node).  Output voxel (b, d, h, w)
+//   takes replica r's voxel (b, d', h', w'), x' = extent - 1 - x where the bit is set.  The item below is mc_accum_item with that
+//   one change in where a replica's group is read: the same softmax, entropy and square per voxel, the same association, so the sums
+//   and the samples are those of the unmirrored entry points on logits un-mirrored beforehand, bit for bit.
+//   m1_tta_views: the stacked input of such a pass, replica r = x mirrored by mask r, one launch.
+// A group of G voxels is read as one contiguous run only inside one W row, so the vector path needs W % G == 0 (and the 16-byte
+// alignment of the unmirrored launchers); with a W mirror the run starts at W - G - w and its voxels are reversed in registers, the
+// classes of a voxel staying in order.  Every other shape runs the same item with G = 1.
+// ---------------------------------------------------------------------------------------------------------------------------------
+template <typename T, int NC, int G, bool U>
+__device__ __forceinline__ void mc_accum_v_item(const T* lg, long long rstride, int R, unsigned long long flips, long long v0, int D,
+                                                int H, int W, float* sum_p, int accumulate, float* samples, float* sum_h, float* sum_pp) {
+    constexpr int E = G * NC, LV = sizeof(T) == 2 ? 8 : 4;
+    constexpr bool VEC = G > 1;
+    const long long e0 = v0 * NC, row = v0 / W, bd = row / H;
+    const int w = (int)(v0 - row * W), h = (int)(row - bd * H);
+    const long long b = bd / D;
+    const int d = (int)(bd - b * D);
+    float old[E], acc[E];
+    float oldq[U ? E : 1], accq[U ? E : 1], oldh[U ? G : 1], acch[U ? G : 1];
+    if (accumulate) mc_ld<E, VEC>(sum_p + e0, old);
+    if constexpr (U) {
+        if (accumulate) {
+            mc_ld<E, VEC>(sum_pp + e0, oldq);
+            mc_ld<G, VEC>(sum_h + v0, oldh);
+        }
+    }
+    for (int r = 0; r < R; ++r) {
+        const unsigned m = (unsigned)(flips >> (3 * r)) & 7u;
+        const int ds = (m & 4u) ? D - 1 - d : d, hs = (m & 2u) ? H - 1 - h : h, ws = (m & 1u) ? W - G - w : w;
+        float v[E];
+        const T* p = lg + (long long)r * rstride + (((b * D + ds) * H + hs) * W + ws) * NC;
+        if constexpr (VEC) {
+#pragma unroll
+            for (int q = 0; q < E / LV; ++q) VecIO<T, LV>::ld(p + q * LV, v + q * LV);
+            if (m & 1u) {                                                        // (the run was read backwards: voxel g <-> G - 1 - g)
+#pragma unroll
+                for (int g = 0; g < G / 2; ++g) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        const float t = v[g * NC + c];
+                        v[g * NC + c] = v[(G - 1 - g) * NC + c];
+                        v[(G - 1 - g) * NC + c] = t;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; ++k) v[k] = Act<T>::ld(p + k);
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) mc_softmax<NC>(v + g * NC);
+        if (samples) mc_st<E, VEC>(samples + (long long)r * rstride + e0, v);
+        if (r == 0) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) acc[k] = v[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; ++k) acc[k] = acc[k] + v[k];
+        }
+        if constexpr (U) {
+            float hh[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) hh[g] = mc_draw_entropy<NC>(v + g * NC);
+#pragma unroll
+            for (int k = 0; k < E; ++k) v[k] = v[k] * v[k];
+            if (r == 0) {
+#pragma unroll
+                for (int k = 0; k < E; ++k) accq[k] = v[k];
+#pragma unroll
+                for (int g = 0; g < G; ++g) acch[g] = hh[g];
+            } else {
+#pragma unroll
+                for (int k = 0; k < E; ++k) accq[k] = accq[k] + v[k];
+#pragma unroll
+                for (int g = 0; g < G; ++g) acch[g] = acch[g] + hh[g];
+            }
+        }
+    }
+    if (accumulate) {
+#pragma unroll
+        for (int k = 0; k < E; ++k) acc[k] = old[k] + acc[k];
+    }
+    mc_st<E, VEC>(sum_p + e0, acc);
+    if constexpr (U) {
+        if (accumulate) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) accq[k] = oldq[k] + accq[k];
+#pragma unroll
+            for (int g = 0; g < G; ++g) acch[g] = oldh[g] + acch[g];
+        }
+        mc_st<E, VEC>(sum_pp + e0, accq);
+        mc_st<G, VEC>(sum_h + v0, acch);
+    }
+}
+
+// M = B * D * H * W voxels in items of G: G divides W (the launcher's vector condition), so it divides M and no item leaves its row
+template <typename T, int NC, int G, bool U>
+__global__ void __launch_bounds__(256) mc_accum_v_kernel(const T* __restrict__ lg, int R, unsigned long long flips, long long M, int D,
+                                                         int H, int W, float* __restrict__ sum_p, float* __restrict__ sum_h,
+                                                         float* __restrict__ sum_pp, int accumulate, float* __restrict__ samples) {
+    const long long items = M / G, rstride = M * NC;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256)
+        mc_accum_v_item<T, NC, G, U>(lg, rstride, R, flips, i * G, D, H, W, sum_p, accumulate, samples, sum_h, sum_pp);
+}
+
+template <typename T, int NC, bool U>
+static int mc_accum_v_launch_nc(const void* logits, int R, unsigned long long flips, long long M, int D, int H, int W, float* sum_p,
+                                float* sum_h, float* sum_pp, int accumulate, float* samples, hipStream_t st) {
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;
+    const bool vec = W % G == 0 && mc_al(logits, 16) && mc_al(sum_p, 16) && mc_al(sum_h, 16) && mc_al(sum_pp, 16) &&
+                     (!samples || mc_al(samples, 16)) && (R == 1 || (M * NC * (long long)sizeof(T)) % 16 == 0);
+    const long long items = vec ? M / G : M;
+    const dim3 grid(m1_grid_for(items, 1)), block(256);
+    const int acc = accumulate != 0;
+    if (vec) hipLaunchKernelGGL((mc_accum_v_kernel<T, NC, G, U>), grid, block, 0, st, (const T*)logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, acc, samples);
+    else hipLaunchKernelGGL((mc_accum_v_kernel<T, NC, 1, U>), grid, block, 0, st, (const T*)logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, acc, samples);
+    return m1_check_launch();
+}
+
+template <typename T, bool U>
+static int mc_accum_v_launch(const void* logits, int R, unsigned long long flips, long long M, int D, int H, int W, int nc, float* sum_p,
+                             float* sum_h, float* sum_pp, int accumulate, float* samples, hipStream_t st) {
+    switch (nc) {
+        case 2: return mc_accum_v_launch_nc<T, 2, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+        case 3: return mc_accum_v_launch_nc<T, 3, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+        default: return mc_accum_v_launch_nc<T, 4, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+    }
+}
+
+// R in 1..16 and no bit of `flips` at or above 3R: M1_OK, else the status both mirror entry points answer
+static int mc_views_check(int R, unsigned long long flips) {
+    if (R <= 0) return M1_ERR_BAD_ARG;
+    if (R > 16) return M1_ERR_UNSUPPORTED;
+    if (flips >> (3 * R)) return M1_ERR_BAD_ARG;
+    return M1_OK;
+}
+
+extern "C" int m1_mc_accum_v(const void* logits, int R, int B, int D, int H, int W, int nc, int dtype, unsigned long long flips,
+                             float* sum_p, float* sum_h, float* sum_pp, int accumulate, float* samples_out, void* stream) {
+    if (m1_debug_skip("mc_accum")) return M1_OK;
+    if (!logits || !sum_p || (sum_h == nullptr) != (sum_pp == nullptr) || B <= 0 || D <= 0 || H <= 0 || W <= 0 ||
+        (dtype != M1_F32 && dtype != M1_BF16))
+        return M1_ERR_BAD_ARG;
+    if (const int rc = mc_views_check(R, flips)) return rc;
+    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
+    if (!mc_al(logits, dtype == M1_BF16 ? 2 : 4) || !mc_al(sum_p, 4) || !mc_al(sum_h, 4) || !mc_al(sum_pp, 4) || !mc_al(samples_out, 4))
+        return M1_ERR_BAD_ARG;
+    if ((double)B * D * H * W > (double)((1ll << 40) / R)) return M1_ERR_BAD_ARG;   // (element offsets stay far inside 63 bits)
+    const long long M = (long long)B * D * H * W;
+    const bool u = sum_h != nullptr;
+    const double el = (double)M * nc;
+    M1ProfScope ps("mc_accum_v", 0.0, el * R * (dtype == M1_BF16 ? 2 : 4) + (u ? 2.0 * el + (double)M : el) * 4 * (accumulate ? 2 : 1) +
+                   (samples_out ? el * R * 4 : 0.0), (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == M1_BF16)
+        return u ? mc_accum_v_launch<bf16_t, true>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st)
+                 : mc_accum_v_launch<bf16_t, false>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st);
+    return u ? mc_accum_v_launch<float, true>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st)
+             : mc_accum_v_launch<float, false>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st);
+}
+
+// The copy in 16-byte chunks of a W row (W * C elements, a whole number of chunks; ET = the element as an unsigned integer): a thread
+// reads one chunk of x once and, per replica, stores it whole to the same place of the (D-, H-) mirrored row, or with a W mirror
+// scatters its K elements to (W - 1 - w) * C + c -- a wave's stores still cover one contiguous run of the row, backwards.
+template <typename ET>
+__global__ void __launch_bounds__(256) tta_views_row_kernel(const uint4* __restrict__ x, long long rows, int D, int H, int W, int C,
+                                                            int cpr, int R, unsigned long long flips, ET* __restrict__ out) {
+    constexpr int K = 16 / (int)sizeof(ET);
+    const long long items = rows * cpr, rowlen = (long long)W * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const long long row = i / cpr, bd = row / H, b = bd / D;
+        const int q = (int)(i - row * cpr), h = (int)(row - bd * H), d = (int)(bd - b * D);
+        union { uint4 v; ET e[K]; } u;
+        u.v = x[i];
+        const int e0 = q * K, w0 = e0 / C, c0 = e0 - w0 * C;
+        for (int r = 0; r < R; ++r) {
+            const unsigned m = (unsigned)(flips >> (3 * r)) & 7u;
+            const int dd = (m & 4u) ? D - 1 - d : d, hd = (m & 2u) ? H - 1 - h : h;
+            ET* dst = out + ((long long)r * rows + (b * D + dd) * H + hd) * rowlen;
+            if (!(m & 1u)) {
+                *reinterpret_cast<uint4*>(dst + e0) = u.v;
+            } else {
+                int w = w0, c = c0;
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    dst[(W - 1 - w) * C + c] = u.e[j];
+                    if (++c == C) { c = 0; ++w; }
+                }
+            }
+        }
+    }
+}
+
+// Every other shape or alignment: one unit (4 or 2 bytes) of one voxel of x to its place in every replica, n units per voxel.
+template <typename UT>
+__global__ void __launch_bounds__(256) tta_views_kernel(const UT* __restrict__ x, long long M, int D, int H, int W, int n, int R,
+                                                        unsigned long long flips, UT* __restrict__ out) {
+    const long long items = M * n;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const long long v0 = i / n, row = v0 / W, bd = row / H, b = bd / D;
+        const int u = (int)(i - v0 * n), w = (int)(v0 - row * W), h = (int)(row - bd * H), d = (int)(bd - b * D);
+        const UT val = x[i];
+        for (int r = 0; r < R; ++r) {
+            const unsigned m = (unsigned)(flips >> (3 * r)) & 7u;
+            const int dd = (m & 4u) ? D - 1 - d : d, hd = (m & 2u) ? H - 1 - h : h, wd = (m & 1u) ? W - 1 - w : w;
+            out[((long long)r * M + ((b * D + dd) * H + hd) * W + wd) * n + u] = val;
+        }
+    }
+}
+
+extern "C" int m1_tta_views(const void* x, int B, int D, int H, int W, int C, int dtype, int R, unsigned long long flips, void* out,
+                            void* stream) {
+    if (m1_debug_skip("tta_views")) return M1_OK;
+    if (!x || !out || B <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || (dtype != M1_F32 && dtype != M1_BF16)) return M1_ERR_BAD_ARG;
+    if (const int rc = mc_views_check(R, flips)) return rc;
+    const int es = dtype == M1_BF16 ? 2 : 4;
+    if (!mc_al(x, es) || !mc_al(out, es)) return M1_ERR_BAD_ARG;
+    if ((double)B * D * H * W * C > (double)((1ll << 40) / R)) return M1_ERR_BAD_ARG;
+    const long long M = (long long)B * D * H * W, vb = (long long)C * es, rb = vb * W;      // (voxels; bytes per voxel, per W row)
+    hipStream_t st = (hipStream_t)stream;
+    M1ProfScope ps("tta_views", 0.0, (double)M * vb * (1.0 + R), st);
+    const dim3 block(256);
+    if (rb % 16 == 0 && rb < (1ll << 31) && mc_al(x, 16) && mc_al(out, 16)) {
+        const long long rows = M / W;
+        const int cpr = (int)(rb / 16);
+        const dim3 grid(m1_grid_for(rows * cpr, 1));
+        if (es == 4) hipLaunchKernelGGL(tta_views_row_kernel<unsigned>, grid, block, 0, st, (const uint4*)x, rows, D, H, W, C, cpr, R, flips, (unsigned*)out);
+        else hipLaunchKernelGGL(tta_views_row_kernel<unsigned short>, grid, block, 0, st, (const uint4*)x, rows, D, H, W, C, cpr, R, flips, (unsigned short*)out);
+        return m1_check_launch();
+    }
+    const int ub = (vb % 4 == 0 && mc_al(x, 4) && mc_al(out, 4)) ? 4 : 2;
+    const int n = (int)(vb / ub);
+    const dim3 grid(m1_grid_for(M * n, 1));
+    if (ub == 4) hipLaunchKernelGGL(tta_views_kernel<unsigned>, grid, block, 0, st, (const unsigned*)x, M, D, H, W, n, R, flips, (unsigned*)out);
+    else hipLaunchKernelGGL(tta_views_kernel<unsigned short>, grid, block, 0, st, (const unsigned short*)x, M, D, H, W, n, R, flips, (unsigned short*)out);
+    return m1_check_launch();
+}

@@ -193,6 +193,8 @@ SIGNATURES = {
     "m1_mc_finish": (_i, [_vp, _i, _i, _ll, _i, _vp, _vp, _vp]),
     "m1_mc_accum_u": (_i, [_vp, _i, _i, _ll, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "m1_mc_finish_u": (_i, [_vp, _vp, _vp, _i, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m1_mc_accum_v": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _u64, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m1_tta_views": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _u64, _vp, _vp]),
     "m1_focal_ws_floats": (_sz, [_i, _ll, _i]),
     "m1_focal_fwd": (_i, [_vp, _vp, _i, C.POINTER(_f), _f, _i, _ll, _i, _i, _vp, _vp, _vp]),
     "m1_focal_bwd": (_i, [_vp, _vp, _i, C.POINTER(_f), _f, _i, _ll, _i, _i, _vp, _vp, _vp]),

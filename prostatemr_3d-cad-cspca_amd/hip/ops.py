@@ -952,6 +952,69 @@ def mc_finish_u(acc, n: int):
     return {"mean": sum_p, "entropy": ent, "expected_entropy": sum_h, "mutual_info": mi, "variance": sum_pp}
 
 
+def _flips(what: str, views, R: Optional[int] = None) -> Tuple[int, int]:
+    """(R, the packed masks of m1_mc_accum_v / m1_tta_views) of ``views``, a sequence of 3-bit mirror masks (bit 0: W, 1: H, 2: D)."""
+    views = [int(v) for v in views]
+    if not 1 <= len(views) <= 16 or (R is not None and len(views) != int(R)):
+        raise RuntimeError(f"{what}: one mask per replica expected (1..16), got {len(views)} masks" + ("" if R is None else f" for R = {R}"))
+    if any(v < 0 or v > 7 for v in views):
+        raise RuntimeError(f"{what}: a view is a mask 0..7 (bit 0 mirrors W, bit 1 H, bit 2 D), got {views}")
+    return len(views), sum(v << (3 * r) for r, v in enumerate(views))
+
+
+def mc_accum_v(logits: torch.Tensor, R: int, views, acc=None, samples: bool = False, uncertainty: bool = False):
+    """``mc_accum`` (``uncertainty=False``: ``acc`` and the result are its sum_p) or ``mc_accum_u`` (``uncertainty=True``: its triple)
+    of a pass whose replica r was computed on the input mirrored by ``views[r]``, a mask 0..7 (bit 0: W, bit 1: H, bit 2: D): the
+    logits (R*B, D, H, W, nc) are read at the mirrored coordinates, so the accumulators and the samples (R, B, D, H, W, nc) are on the
+    caller's own grid (m1_mc_accum_v).  Equal, bit for bit, to the plain op on logits that were flipped back beforehand."""
+    what = "mc_accum_v"
+    _no_grad_only(what)
+    R = int(R)
+    if logits.dim() != 5 or R < 1 or int(logits.shape[0]) % R:
+        raise RuntimeError(f"{what}: logits {tuple(logits.shape)} are not (R*B, D, H, W, nc) with R = {R}")
+    R, flips = _flips(what, views, R)
+    B, (D, H, W, nc) = int(logits.shape[0]) // R, (int(v) for v in logits.shape[1:])
+    shape = (B, D, H, W, nc)
+    shapes = (shape, shape[:-1], shape) if uncertainty else (shape,)
+    names = ("sum_p", "sum_h", "sum_pp")
+    if acc is None:
+        add, sums = 0, None
+    else:
+        add, sums = 1, (tuple(acc) if uncertainty else (acc,))
+        if len(sums) != len(shapes) or not all(isinstance(t, torch.Tensor) for t in sums):
+            raise RuntimeError(f"{what}: acc must be " + ("(sum_p, sum_h, sum_pp)" if uncertainty else "the sum_p tensor"))
+        for t, s, n in zip(sums, shapes, names):
+            if t.dtype != torch.float32 or tuple(t.shape) != s:
+                raise RuntimeError(f"{what}: {n} must be fp32 {s}, got {t.dtype} {tuple(t.shape)}")
+    draws = samples if isinstance(samples, torch.Tensor) else None
+    if draws is not None and (draws.dtype != torch.float32 or tuple(draws.shape) != (R, *shape)):
+        raise RuntimeError(f"{what}: samples must be fp32 {(R, *shape)}, got {draws.dtype} {tuple(draws.shape)}")
+    _req(logits, draws, *(sums or ()))
+    if sums is None:
+        sums = tuple(torch.empty(s, dtype=torch.float32, device=logits.device) for s in shapes)
+    if draws is None and samples:
+        draws = torch.empty((R, *shape), dtype=torch.float32, device=logits.device)
+    sp, sh, sq = sums if uncertainty else (sums[0], None, None)
+    L.check(L.load().m1_mc_accum_v(_p(logits), R, B, D, H, W, nc, _dt(logits), flips, _p(sp), _p(sh), _p(sq), add, _p(draws), _stream()),
+            "m1_mc_accum_v")
+    res = sums if uncertainty else sums[0]
+    return res if draws is None else (res, draws)
+
+
+def tta_views(x: torch.Tensor, views) -> torch.Tensor:
+    """(len(views)*B, D, H, W, C), replica-major: replica r is ``x`` (B, D, H, W, C) fp32 / bf16 mirrored by the mask ``views[r]``
+    (m1_tta_views) -- ``x.repeat`` and the per-view flips in one launch."""
+    _no_grad_only("tta_views")
+    if x.dim() != 5:
+        raise RuntimeError(f"tta_views: x must be (B, D, H, W, C), got {tuple(x.shape)}")
+    R, flips = _flips("tta_views", views)
+    _req(x)
+    B, D, H, W, Cn = (int(v) for v in x.shape)
+    out = torch.empty((R * B, D, H, W, Cn), dtype=x.dtype, device=x.device)
+    L.check(L.load().m1_tta_views(_p(x), B, D, H, W, Cn, _dt(x), R, flips, _p(out), _stream()), "m1_tta_views")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------
 # Per-case scoring of a validation batch (validate.hip; validation.validate)
 # ---------------------------------------------------------------------------------------------------------

@@ -28,7 +28,8 @@ What differs from the reference, and why (its harness bugs a
     ``--UNET_PROBA_ITER`` and ``--METRICS_DIR`` and leaves the callbacks that would use them open (T:240-245).  Here ``--VALIDATE 1``
     (a flag of this build, default 0: the trainer then makes exactly the calls it made before) adds ``callbacks.Validate`` after
     ``WeightsSaver``: every ``VALIDATE_PER_N_EPOCHS`` epochs from ``VALIDATE_MIN_EPOCH`` on, ``validation.validate`` scores the
-    held-out cases with ``UNET_PROBA_ITER`` draws per case (``predict_mc``: fresh dropout masks and latent samples) and appends a row
+    held-out cases with ``UNET_PROBA_ITER`` draws per case (``predict_mc``: fresh dropout masks and latent samples; with
+    ``--VALIDATE_TTA id w ...`` that many draws of every mirrored view, un-mirrored and averaged in the same accumulators) and appends a row
     to ``METRICS_DIR + NAME + '/F<fold>/validation.csv'``; the ``val_*`` numbers also enter ``fit``'s history.  The cases come from
     ``VALID_XLSX_PREFIX<fold>.xlsx`` with ``--DATA_FEED sheet`` (``device_batches(mode='valid')``), else from ``--VALID_NPY_DIR`` or
     ``--SYNTHETIC_VALID_SAMPLES`` synthetic cases seeded apart from the training cases.  The validation loss is the detection term
@@ -143,6 +144,8 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--SEED', type=int, default=0)
     # This build's train-time validation (callbacks.Validate): off by default
     prsr.add_argument('--VALIDATE', type=int, default=0, help="1: validate every VALIDATE_PER_N_EPOCHS epochs from VALIDATE_MIN_EPOCH on")
+    prsr.add_argument('--VALIDATE_TTA', type=str, default=[], nargs='*',
+                      help="mirrored views of the validation predictions: id, w, h, d, hw, ... (unets.networks.tta_views); none = off")
     prsr.add_argument('--VALID_NPY_DIR', type=str, default=None, help="--DATA_FEED cases: directory of held-out image_*.npy / label_*.npy pairs")
     prsr.add_argument('--SYNTHETIC_VALID_SAMPLES', type=int, default=4, help="held-out synthetic cases per fold when no .npy directory is given")
     # This build's guarded optimiser step (optim.Adam): all off by default
@@ -150,6 +153,16 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--GRAD_CLIP_VALUE', type=float, default=0.0, help="tf.keras clipvalue per gradient element, 0 = off")
     prsr.add_argument('--SKIP_NONFINITE', type=int, default=0, help="1: a step whose gradient norm is NaN / Inf changes nothing")
     return prsr
+
+
+def validate_tta(args) -> dict:
+    """``{"tta": views}`` of --VALIDATE_TTA for callbacks.Validate, checked here so that a typo stops the run before the first epoch;
+    ``{}`` without views: the callback is then built as it is without the flag."""
+    views = tuple(args.VALIDATE_TTA or ())
+    if not views:
+        return {}
+    unets.networks.tta_views(views)
+    return {"tta": views}
 
 
 def optimizer_kwargs(args) -> dict:
@@ -286,7 +299,8 @@ def build_callbacks(args, f: int, model, fold_dir: str, init_epoch: int, valid_f
         out.append(cbs.Validate(model, feed, steps, every_n_epochs=args.VALIDATE_PER_N_EPOCHS, min_epoch=args.VALIDATE_MIN_EPOCH,
                                 n_draws=args.UNET_PROBA_ITER, train_obj=args.TRAIN_OBJ,
                                 metrics_dir=os.path.join(args.METRICS_DIR + args.NAME, 'F' + str(f + 1)), init_epoch=init_epoch,
-                                rank=rank, world=world, alpha=list(args.FOCAL_LOSS_ALPHA), gamma=args.FOCAL_LOSS_GAMMA))
+                                rank=rank, world=world, alpha=list(args.FOCAL_LOSS_ALPHA), gamma=args.FOCAL_LOSS_GAMMA,
+                                **validate_tta(args)))
     return out
 
 

@@ -922,27 +922,49 @@ class M1(LoadableModel):
                     o = outer.m1_model(outer._prep(x))
                     return o['y_softmax'][..., :nc]
 
-            def predict(self, x, **kw):
-                return self.forward(x, **kw)
+            def predict(self, x, tta=None, **kw):
+                """``forward``; with ``tta`` (see ``tta_views``) the mean over the mirrored views, each un-mirrored: what
+                ``predict_mc(x, 1, draws_per_pass=len(views), tta=views)`` returns as "mean" from the current state, one stacked pass.
+                The {seed, step} state does not move."""
+                views = tta_views(tta)
+                if views is None:
+                    return self.forward(x, **kw)
+                if kw.get("eps_q") is not None:
+                    raise ValueError("predict: eps_q has no part in a prediction with tta")
+                sums, _ = self._mc_passes(x, 1, len(views), eps_p=kw.get("eps_p"), advance=False, views=views)
+                means = [r["mean"] for r in _mc_results(sums, None, len(views), False)]
+                return means if outer.references.cascaded != False else means[0]  # noqa: E712
 
-            def _mc_passes(self, x, n, R, uncertainty=False, eps_p=None, carry=None, total=0, first=0, advance=True):
+            def _mc_passes(self, x, n, R, uncertainty=False, eps_p=None, carry=None, total=0, first=0, advance=True, views=None):
                 """``n // R`` passes of ``R`` replicas each, folded into the accumulators ``carry`` = (sums, draws) of an earlier call
                 (another model's, see ``Ensemble``) or into fresh ones; returns (sums, draws), one entry per stage.  sums[j] is
                 ops.mc_accum's sum_p, or ops.mc_accum_u's triple with ``uncertainty``.  ``total`` > 0 asks for the per-draw
                 probabilities: draws[j] is (total, B, D, H, W, nc), and this call fills [first, first + n).  The {seed, step} state
-                advances once per pass unless ``advance`` is False."""
+                advances once per pass unless ``advance`` is False.
+                ``views`` (mirror masks, ``tta_views``): len(views) * n draws, view-major, in (len(views) * n) // R passes of R
+                consecutive draws; a pass's input is ops.tta_views of its draws' masks (both stages of a cascaded model alike) and
+                its logits go through ops.mc_accum_v, which un-mirrors them; the call fills [first, first + len(views) * n)."""
                 prob = outer.references.probabilistic
                 casc = outer.references.cascaded != False  # noqa: E712
                 rep = (lambda t: t.repeat(R, 1, 1, 1, 1)) if R > 1 else (lambda t: t)
                 accum = ops.mc_accum_u if uncertainty else ops.mc_accum
                 sums, draws = carry if carry is not None else (None, None)
                 with torch.no_grad():
+                    if views is not None:                                  # (the stacks come from ops.tta_views, pass by pass)
+                        rep = lambda t: t  # noqa: E731
                     if casc:
                         x1, x2 = outer._cascade_inputs(x)
                         xin = (rep(outer._prep(x1, channels=outer.input_channels)), rep(outer._prep(x2, channels=outer.input_channels)))
                     else:
                         xin = rep(outer._prep(x))
-                    for k in range(n // R):
+                    base, mirrored, passes = xin, {}, (n if views is None else len(views) * n) // R
+                    for k in range(passes):
+                        if views is not None:
+                            masks = tuple(views[j // n] for j in range(k * R, (k + 1) * R))
+                            if masks not in mirrored:
+                                mirrored[masks] = tuple(ops.tta_views(t, masks) for t in base) if casc else ops.tta_views(base, masks)
+                            xin = mirrored[masks]
+                            accum = lambda l, r, acc, samples, mk=masks: ops.mc_accum_v(l, r, mk, acc, samples, uncertainty)  # noqa: E731
                         if casc:
                             outer._forward_cascaded(xin, eps_p=eps_p, with_infer=prob)
                             outs = outer._last_cascade
@@ -962,7 +984,7 @@ class M1(LoadableModel):
                             outer.advance_rng()
                 return sums, draws
 
-            def predict_mc(self, x, n_draws, draws_per_pass=1, return_samples=False, eps_p=None, uncertainty=False):
+            def predict_mc(self, x, n_draws, draws_per_pass=1, return_samples=False, eps_p=None, uncertainty=False, tta=None):
                 """Monte-Carlo inference (the reference's --UNET_PROBA_ITER, train_model.py:72): ``n_draws`` hypotheses of ``predict`` --
                 fresh dropout masks and, for the probabilistic model, fresh z ~ P at every level -- folded into
                 {"mean": (B,D,H,W,nc) fp32, "entropy": (B,D,H,W) fp32 in nats (scipy.stats.entropy of the mean)
@@ -977,16 +999,24 @@ class M1(LoadableModel):
                 "expected_entropy" (B,D,H,W) = the mean of the draws' own entropies (what every draw agrees is ambiguous),
                 "mutual_info" (B,D,H,W) = entropy - expected_entropy >= 0 (what the draws disagree on) and "variance" (B,D,H,W,nc),
                 the population variance of the draws per class.  mean, entropy, samples and the state after the call are those of
-                the call without it; one draw gives mutual_info = variance = +0."""
-                n, R = _mc_counts(n_draws, draws_per_pass)
-                if eps_p is not None and n > 1:
+                the call without it; one draw gives mutual_info = variance = +0.
+                ``tta`` (see ``tta_views``): test-time augmentation by mirroring.  Every view takes ``n_draws`` draws, N = views *
+                n_draws in all, view-major (view v owns draws [v * n_draws, (v + 1) * n_draws)), cut into passes of ``draws_per_pass``
+                consecutive draws, which must divide N; a pass may mix views.  The input of a pass is ops.tta_views, its logits go
+                to ops.mc_accum_v, which reads them at the mirrored coordinates: the sums, the maps and the samples (N,B,D,H,W,nc)
+                are on the caller's grid, and no un-mirrored tensor exists in between.  ``tta=None`` is the call without it;
+                ``tta=("",)`` gives its bits and its final state."""
+                views = tta_views(tta)
+                n, R = _mc_counts(n_draws, draws_per_pass, views)
+                N = n * (len(views) if views else 1)
+                if eps_p is not None and N > 1:
                     raise ValueError("predict_mc: injected eps_p with n_draws > 1 would repeat one draw n_draws times")
-                sums, draws = self._mc_passes(x, n, R, uncertainty, eps_p, total=n if return_samples else 0)
-                res = _mc_results(sums, draws, n, uncertainty)
+                sums, draws = self._mc_passes(x, n, R, uncertainty, eps_p, total=N if return_samples else 0, views=views)
+                res = _mc_results(sums, draws, N, uncertainty)
                 return res if outer.references.cascaded != False else res[0]  # noqa: E712
 
             def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
-                             uncertainty=False, **prepare_kw):
+                             uncertainty=False, tta=None, **prepare_kw):
                 """From a raw scan to a prediction on the scan's own grid: preprocess.prepare_scan to the model's input size, ``predict``
                 (n_draws == 1) or ``predict_mc``, then preprocess.restore of the result.  ``raw``: (B,d,h,w,C) fp32 / int16 on the
                 device at ``spacing`` (cascaded: the pair or dict of the two stages' scans, both on one grid); ``prepare_kw`` goes to
@@ -995,11 +1025,11 @@ class M1(LoadableModel):
                 of the restored softmax, with ``labels``], "network": what predict / predict_mc returned on the network's grid}; a
                 cascaded model returns [stage 1, stage 2] of these.  ``uncertainty``: the call goes through ``predict_mc(...,
                 uncertainty=True)`` even with one draw, and the result gains "expected_entropy" and "mutual_info" (B,d,h,w), restored
-                as the entropy is, and "variance" (B,d,h,w,nsel), restored with the channel selection of the mean.  Host composition
-                only (``_predict_scan``, shared with ``Ensemble``)."""
+                as the entropy is, and "variance" (B,d,h,w,nsel), restored with the channel selection of the mean.  ``tta`` goes to
+                ``predict`` / ``predict_mc``.  Host composition only (``_predict_scan``, shared with ``Ensemble``)."""
                 casc = outer.references.cascaded != False  # noqa: E712
                 return _predict_scan(self, outer.input_spatial_dims, outer._cascade_inputs if casc else None, raw, spacing, out_spacing,
-                                     n_draws, draws_per_pass, percentile, channels, labels, uncertainty, prepare_kw)
+                                     n_draws, draws_per_pass, percentile, channels, labels, uncertainty, prepare_kw, tta)
         return _Detect()
 
     # ---- networks.py:209-223 ---------------------------------------------------------------------------------
@@ -1079,11 +1109,49 @@ class M1(LoadableModel):
 # ============================================================================================================
 # Monte-Carlo inference: what the detect model and an ensemble of detect models share (host composition only)
 # ============================================================================================================
-def _mc_counts(n_draws, draws_per_pass):
+def _mc_counts(n_draws, draws_per_pass, views=None):
     n, R = int(n_draws), int(draws_per_pass)
+    if views is not None:
+        if n < 1 or R < 1 or (len(views) * n) % R:
+            raise ValueError(f"predict_mc: n_draws >= 1 and draws_per_pass dividing views * n_draws = {len(views) * n} expected, got "
+                             f"{n_draws} / {draws_per_pass}")
+        if R > 16:
+            raise ValueError(f"predict_mc: at most 16 draws per pass with tta (one mirror mask each), got {R}")
+        return n, R
     if n < 1 or R < 1 or n % R:
         raise ValueError(f"predict_mc: n_draws >= 1 and draws_per_pass dividing it expected, got {n_draws} / {draws_per_pass}")
     return n, R
+
+
+_TTA_BITS = {"w": 1, "h": 2, "d": 4}
+
+
+def tta_views(spec):
+    """The mirror masks of a test-time augmentation: ``None`` (no TTA) or a non-empty sequence of views, each a string over the letters
+    ``d``, ``h``, ``w`` naming the axes it mirrors (``""`` or ``"id"``: the identity), e.g. ``("", "w")`` or ``("", "w", "h", "hw")``
+    -> the tuple of 3-bit masks (w = 1, h = 2, d = 4) that ops.tta_views / ops.mc_accum_v take.  The identity is a view like any
+    other: it is in only if listed.  ValueError for an unknown or repeated letter, a view listed twice, or no view at all."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        raise ValueError(f"tta: a sequence of views expected, e.g. ('', 'w'), got the string {spec!r}")
+    masks = []
+    for v in spec:
+        if isinstance(v, str):
+            letters = "" if v == "id" else v.lower()
+            if any(c not in _TTA_BITS for c in letters) or len(set(letters)) != len(letters):
+                raise ValueError(f"tta: a view is made of the letters d, h, w, each at most once ('' or 'id': identity), got {v!r}")
+            m = sum(_TTA_BITS[c] for c in letters)
+        elif isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= int(v) <= 7:
+            m = int(v)
+        else:
+            raise ValueError(f"tta: a view is a string over d, h, w (or its mask 0..7), got {v!r}")
+        if m in masks:
+            raise ValueError(f"tta: view {v!r} is listed twice")
+        masks.append(m)
+    if not masks:
+        raise ValueError("tta: at least one view expected (None switches it off)")
+    return tuple(masks)
 
 
 def _mc_results(sums, draws, n, uncertainty):
@@ -1103,7 +1171,7 @@ def _mc_results(sums, draws, n, uncertainty):
 
 
 def _predict_scan(predictor, dims, cascade_inputs, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile, channels, labels,
-                  uncertainty, prepare_kw):
+                  uncertainty, prepare_kw, tta=None):
     """``predict_scan`` of anything with ``predict`` / ``predict_mc``: prepare_scan to the network's grid ``dims``, the prediction,
     preprocess.restore of every map.  ``cascade_inputs``: the cascaded model's splitter of ``raw`` into its two scans, else None."""
     from .. import preprocess as PP
@@ -1114,10 +1182,11 @@ def _predict_scan(predictor, dims, cascade_inputs, raw, spacing, out_spacing, n_
         raise ValueError(f"predict_scan: both stages' scans must share one grid, got {[tuple(r.shape) for r in raws]}")
     xs = [PP.prepare_scan(r, spacing, out_spacing, dims, percentile=percentile, **prepare_kw)[0] for r in raws]
     x = xs if casc else xs[0]
+    kw = {} if tta is None else {"tta": tta}
     if uncertainty:
-        net = predictor.predict_mc(x, n_draws, draws_per_pass, uncertainty=True)
+        net = predictor.predict_mc(x, n_draws, draws_per_pass, uncertainty=True, **kw)
     else:
-        net = predictor.predict(x) if int(n_draws) == 1 else predictor.predict_mc(x, n_draws, draws_per_pass)
+        net = predictor.predict(x, **kw) if int(n_draws) == 1 else predictor.predict_mc(x, n_draws, draws_per_pass, **kw)
     res = []
     for o in (net if casc else [net]):
         mean = o["mean"] if isinstance(o, dict) else o
@@ -1187,27 +1256,32 @@ class Ensemble:
             models.append(m)
         return cls(models, seed=seed)
 
-    def _fold(self, x, n, R, uncertainty, samples, advance=True):
-        carry, total = None, len(self.detectors) * n if samples else 0
+    def _fold(self, x, n, R, uncertainty, samples, advance=True, views=None):
+        per = n * (len(views) if views else 1)                        # (draws per member)
+        carry, total = None, len(self.detectors) * per if samples else 0
         for i, dm in enumerate(self.detectors):
-            carry = dm._mc_passes(x, n, R, uncertainty, carry=carry, total=total, first=i * n, advance=advance)
+            carry = dm._mc_passes(x, n, R, uncertainty, carry=carry, total=total, first=i * per, advance=advance, views=views)
         return carry
 
-    def predict(self, x):
+    def predict(self, x, tta=None):
         """(B,D,H,W,nc) fp32: the mean of the members' ``predict(x)``, one draw each at the member's current state (which does not
-        move, as in ``predict``)."""
-        sums, _ = self._fold(x, 1, 1, False, False, advance=False)
-        return _mc_results(sums, None, len(self.detectors), False)[0]["mean"]
+        move, as in ``predict``); with ``tta`` the mean of the members' ``predict(x, tta=tta)``, one stacked pass per member."""
+        views = tta_views(tta)
+        nv = len(views) if views else 1
+        sums, _ = self._fold(x, 1, nv, False, False, advance=False, views=views)
+        return _mc_results(sums, None, len(self.detectors) * nv, False)[0]["mean"]
 
-    def predict_mc(self, x, n_draws, draws_per_pass=1, uncertainty=False, return_samples=False):
+    def predict_mc(self, x, n_draws, draws_per_pass=1, uncertainty=False, return_samples=False, tta=None):
         """``predict_mc`` of the detect model over N = members * n_draws draws, ``n_draws`` per member; "samples" (N,B,D,H,W,nc) are
-        member-major (member i's draws at [i * n_draws, (i + 1) * n_draws))."""
-        n, R = _mc_counts(n_draws, draws_per_pass)
-        sums, draws = self._fold(x, n, R, uncertainty, return_samples)
-        return _mc_results(sums, draws, len(self.detectors) * n, uncertainty)[0]
+        member-major (member i's draws at [i * n_draws, (i + 1) * n_draws)).  With ``tta``: N = members * views * n_draws, member-major,
+        then view-major, every member's passes cut as in its own ``predict_mc(..., tta=tta)``."""
+        views = tta_views(tta)
+        n, R = _mc_counts(n_draws, draws_per_pass, views)
+        sums, draws = self._fold(x, n, R, uncertainty, return_samples, views=views)
+        return _mc_results(sums, draws, len(self.detectors) * n * (len(views) if views else 1), uncertainty)[0]
 
     def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
-                     uncertainty=False, **prepare_kw):
+                     uncertainty=False, tta=None, **prepare_kw):
         """``predict_scan`` of the detect model, with this ensemble's ``predict`` / ``predict_mc`` in the middle."""
         return _predict_scan(self, self.input_spatial_dims, None, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile,
-                             channels, labels, uncertainty, prepare_kw)
+                             channels, labels, uncertainty, prepare_kw, tta)

@@ -25,6 +25,7 @@ import torch
 
 from . import detection, surface_distance
 from .hip import ops
+from .unets.networks import tta_views
 
 K_EPSILON = 1e-7
 DEFAULT_SPACING = (3.0, 0.5, 0.5)            # mm in (D,H,W) order: the grid of the README's model
@@ -122,7 +123,8 @@ def summarise(cases: Sequence[dict], train_obj: str, with_entropy: bool = True) 
 
 # ---- the pass ----------------------------------------------------------------------------------------------------------------------
 def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws_per_pass: int = 1,
-             alpha: Sequence[float] = (0.25, 0.75), gamma: float = 2.0, spacing=None, rank: int = 0, world: int = 1) -> dict:
+             alpha: Sequence[float] = (0.25, 0.75), gamma: float = 2.0, spacing=None, rank: int = 0, world: int = 1,
+             tta=None) -> dict:
     """``steps`` batches of ``batches`` (an iterator of ``({"image": x}, {"detection": y, ...})`` as the feeds yield them, y one-hot)
     through ``model.get_detect_model()`` -> the dict of ``summarise``.
 
@@ -132,6 +134,9 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
     n_true[1] > 0, score: the case's largest confidence) and the sensitivities at 0.5 / 1 / 2 false positives per case follow at the
     end.  'zonal': the argmax labels go to ``surface_distance.surface_metrics`` with ``spacing`` (mm, (D,H,W) order; default
     (3.0, 0.5, 0.5)); Dice, HD95 and ASSD per class are NaN-aware means over the cases.
+
+    ``tta`` (``unets.networks.tta_views``: mirrored views, e.g. ``("", "w")``): a batch goes through ``predict_mc(x, n_draws,
+    draws_per_pass, tta=views)``, views * n_draws draws in all, and the entropy is scored whenever that is more than one draw.
 
     The loss reported as ``val_focal`` is the detection term on the MC mean alone: no KL, no L2 (module docstring).
 
@@ -145,6 +150,8 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
     if model.references.cascaded != False:  # noqa: E712
         raise NotImplementedError("validate: a cascaded model returns two predictions per case; only the standalone model is scored")
     n, steps = int(n_draws), int(steps)
+    views = tta_views(tta)
+    N = n * (len(views) if views else 1)                                   # draws behind one mean
     spacing = DEFAULT_SPACING if spacing is None else tuple(float(s) for s in spacing)
     saved_rng, was_training = model.rng_state.clone(), model.training
     detect = model.get_detect_model()
@@ -157,7 +164,10 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
                 bx, by = next(it)
                 y = by["detection"] if isinstance(by, dict) else by
                 y = y.contiguous()
-                if n == 1:
+                if views is not None:
+                    o = detect.predict_mc(bx, n, draws_per_pass, tta=views)
+                    mean, ent = o["mean"], (o["entropy"] if N > 1 else None)
+                elif n == 1:
                     mean, ent = detect.predict(bx), None
                 else:
                     o = detect.predict_mc(bx, n, draws_per_pass)
@@ -200,4 +210,4 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
         if rank != 0:
             return {}
         cases = merge_case_records(gathered)
-    return summarise(cases, train_obj, with_entropy=n > 1)
+    return summarise(cases, train_obj, with_entropy=N > 1)
