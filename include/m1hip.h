@@ -773,6 +773,37 @@ size_t m1_val_score_ws(int B, long long voxels, int K);
 int m1_val_score(const float* p, const void* y, int y_dtype, const float* entropy, const float* alpha, float gamma, int B,
                  long long voxels, int K, m1_val_record_t* records, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Calibration record of a validation batch (no reference counterpart; calibration.py: ECE, MCE, Brier, NLL, referral) ----
+ * One streaming pass (csrc/calibrate.hip) over p (B, voxels, K) fp32 or bf16 (p_dtype: enum m1_dtype) -- the softmax, or the mean of
+ * n draws --, label (B, voxels) uint8 class indices, mask (B, voxels) uint8 or NULL (0 skips the voxel, uncounted) and unc
+ * (B, voxels) fp32 or NULL (entropy, mutual information, ...) leaves one record of m1_cal_record_slots(K, bins) = 8 + 3 * bins * (K + 2)
+ * unsigned 64-bit integers per case.  2 <= K <= 4, 1 <= bins = M <= 64, voxels < 2^27.
+ * Per voxel, am = argmax of p (the lowest index among equals, as np.argmax), conf = p[am], y = label:
+ *   a voxel with a NaN p[c], or a NaN unc, counts in n_invalid and nowhere else; otherwise one with y >= K (an ignore label) counts
+ *   in n_ignored and nowhere else; the rest count in n_valid and in everything below.
+ *   fx(v)  = floor(max(v, 0) as a double * 2^32): sums of real quantities are 2^-32 fixed point (exact for an fp32 v >= 2^-9)
+ *   bin(v) = min(M - 1, (int)clip(v * (float)M, 0, M)), the product one fp32 multiply
+ * Slots:
+ *   [0] n_valid  [1] n_invalid  [2] n_ignored
+ *   [3] nll            += fx(-log((double)max(p[y], 1e-7f))), the log in fp64, p as given (no renormalisation)
+ *   [4 + c] brier[c]   += fx(d * d), d = (double)p[c] - (y == c); c < 4, zero for c >= K
+ *   then K + 2 histograms of 3 * M slots each, histogram h at 8 + 3 * M * h: count[M], sum[M], hits[M]
+ *   h = 0         top:    at bin(conf)      count += 1, sum += fx(conf),      hits += (am == y)
+ *   h = 1 + c     cls[c]: at bin(p[c])      count += 1, sum += fx(p[c]),      hits += (y == c)
+ *   h = K + 1     unc:    at bin of u       count += 1, sum += fx(max(u, 0)), hits += (am != y); all zero without unc.
+ *                 Its bin is min(M - 1, (int)clip(u * u_scale, 0, M)), u_scale = (float)(M / u_max) computed by the caller.
+ * p and unc are expected finite (p a probability, u <= 16.2): nothing then overflows.  Every accumulator is an integer, so the
+ * record does not depend on the order of the additions and repeats bit for bit; only nll depends on the device's fp64 log.
+ * Two launches: a kernel zero-fills the records (no memset node), then the scoring kernel (grid = f(B, voxels, M1_EW_BLOCKS)) adds
+ * per-block LDS histograms into them with 64-bit integer atomics.  No host read, no float atomics; pointer alignment only chooses
+ * the width of the loads.  NULL p / label / records, a pointer not aligned to its element (records: 8 bytes), a p_dtype outside the
+ * enum, B or voxels <= 0, voxels >= 2^27, K or bins out of range, unc with a u_scale that is not positive and finite:
+ * M1_ERR_BAD_ARG; B > 65535: M1_ERR_UNSUPPORTED; all before any launch.  m1_cal_record_slots is a pure host call, 0 when K or
+ * bins is out of range. */
+size_t m1_cal_record_slots(int K, int bins);
+int m1_cal_score(const void* p, int p_dtype, const unsigned char* label, const unsigned char* mask, const float* unc, float u_scale,
+                 int B, long long voxels, int K, int bins, unsigned long long* records, void* stream);
+
 /* Deferred folds of the weight-gradient partial copies (no reference counterpart; the reference's tf.GradientTape sums weight
  * gradients inside each op).  m1_conv3d_wgrad / m1_convT3d_wgrad split the voxels over blocks, every block stores its partial
  * tile into a copy inside `ws`, and a fold kernel adds the copies into dw / db in a fixed order.  After m1_wgrad_defer(1) the

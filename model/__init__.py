@@ -1,5 +1,5 @@
 """Reference-shaped import path: ``import model.unets as unets; import model.losses as losses`` (as in the
-reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators``, ``model.preprocess``, ``model.detection``, ``model.surface_distance`` and ``model.validation`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
+reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators``, ``model.preprocess``, ``model.detection``, ``model.surface_distance``, ``model.calibration`` and ``model.validation`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
 import importlib
 import os
 import sys
@@ -17,6 +17,7 @@ data_generators = _pkg.data_generators
 preprocess = _pkg.preprocess
 detection = _pkg.detection
 surface_distance = _pkg.surface_distance
+calibration = _pkg.calibration
 validation = _pkg.validation
 sys.modules[__name__ + ".unets"] = unets
 sys.modules[__name__ + ".unets.networks"] = unets.networks
@@ -28,4 +29,5 @@ sys.modules[__name__ + ".data_generators"] = data_generators
 sys.modules[__name__ + ".preprocess"] = preprocess
 sys.modules[__name__ + ".detection"] = detection
 sys.modules[__name__ + ".surface_distance"] = surface_distance
+sys.modules[__name__ + ".calibration"] = calibration
 sys.modules[__name__ + ".validation"] = validation

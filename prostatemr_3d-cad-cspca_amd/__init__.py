@@ -20,7 +20,8 @@ from . import data_generators  # noqa: F401
 from . import preprocess     # noqa: F401
 from . import detection      # noqa: F401
 from . import surface_distance  # noqa: F401
+from . import calibration    # noqa: F401
 from . import validation     # noqa: F401
 
 __all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp", "augmentations", "data_generators", "preprocess", "detection",
-           "surface_distance", "validation"]
+           "surface_distance", "calibration", "validation"]

@@ -123,6 +123,11 @@ M1_VAL_SLOTS, M1_VAL_MAX_K = 40, 4
 VAL_HEAD_KEYS = ("focal", "entropy_sum", "entropy_fg_sum", "n_voxels", "n_fg")
 VAL_CLASS_KEYS = ("sum_p", "sum_y", "sum_py", "n_pred", "n_true", "n_both", "p_max")
 
+# the record of m1_cal_score: 8 header slots, then K + 2 histograms (top, cls[0..K), unc) of count[M], sum[M], hits[M]
+M1_CAL_HEAD, M1_CAL_MIN_K, M1_CAL_MAX_K, M1_CAL_MAX_BINS, M1_CAL_MAX_VOXELS = 8, 2, 4, 64, 1 << 27
+CAL_HEAD_KEYS = ("n_valid", "n_invalid", "n_ignored", "nll")
+CAL_HIST_KEYS = {"top": ("count", "conf_sum", "correct"), "cls": ("count", "p_sum", "pos"), "unc": ("count", "u_sum", "errors")}
+
 # enum m1_label_objective / m1_feed_mode
 M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
 M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
@@ -239,6 +244,8 @@ SIGNATURES = {
     "m1_step_advance_ctl": (_i, [_vp, _vp, _vp]),
     "m1_val_score_ws": (_sz, [_i, _ll, _i]),
     "m1_val_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(_f), _f, _i, _ll, _i, _vp, _vp, _sz, _vp]),
+    "m1_cal_record_slots": (_sz, [_i, _i]),
+    "m1_cal_score": (_i, [_vp, _i, _vp, _vp, _vp, _f, _i, _ll, _i, _i, _vp, _vp]),
     "m1_wgrad_defer": (_i, [_i]),
     "m1_wgrad_fold_pending": (_i, [_vp]),
     "m1_wgrad_fold_drop": (_i, []),

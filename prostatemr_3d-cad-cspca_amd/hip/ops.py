@@ -1066,6 +1066,78 @@ def read_val_records(records: torch.Tensor, K: int = L.M1_VAL_MAX_K) -> list:
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Calibration record of a validation batch (calibrate.hip; calibration.reliability)
+# ---------------------------------------------------------------------------------------------------------
+def cal_record_slots(K: int, bins: int) -> int:
+    """Unsigned 64-bit slots of one case's calibration record, 8 + 3 * bins * (K + 2) (host only); raises when K is outside 2..4 or
+    bins outside 1..64."""
+    n = int(L.load().m1_cal_record_slots(int(K), int(bins)))
+    if n == 0:
+        raise RuntimeError(f"cal_score: K must be in {L.M1_CAL_MIN_K}..{L.M1_CAL_MAX_K} and bins in 1..{L.M1_CAL_MAX_BINS}, got K = {K}, "
+                           f"bins = {bins}")
+    return n
+
+
+def cal_score(p: torch.Tensor, label: torch.Tensor, bins: int, mask: Optional[torch.Tensor] = None, unc: Optional[torch.Tensor] = None,
+              u_max: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One calibration record per case (m1_cal_score, include/m1hip.h) from ``p`` (B,...,K) fp32 or bf16, ``label`` (B,...) uint8 class
+    indices, ``mask`` (B,...) uint8 or None (0 skips the voxel) and ``unc`` (B,...) fp32 or None with its upper end ``u_max`` (required
+    with ``unc``) -> (B, cal_record_slots(K, bins)) int64 on the device, holding the unsigned 64-bit slots.  ``out``: a contiguous
+    int64 tensor of that shape to write into.  Nothing is read back: ``read_cal_records`` is the host read.  Every argument is
+    checked before anything is launched (RuntimeError; a ``u_max`` that is not positive and finite: calibration.u_scale's ValueError)."""
+    _no_grad_only("cal_score")
+    _req(p, label, mask, unc, out)
+    if p.dtype not in (torch.float32, torch.bfloat16) or p.dim() < 2:
+        raise RuntimeError(f"cal_score: p must be fp32 or bf16 (B,...,K), got {p.dtype} {tuple(p.shape)}")
+    B, K, M = int(p.shape[0]), int(p.shape[-1]), int(bins)
+    slots = cal_record_slots(K, M)
+    V = p.numel() // max(B * K, 1)
+    if B < 1 or V < 1 or V >= L.M1_CAL_MAX_VOXELS:
+        raise RuntimeError(f"cal_score: 1 <= voxels per case < 2^27 and B >= 1 expected, got p {tuple(p.shape)}")
+    for name, t in (("label", label), ("mask", mask)):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != tuple(p.shape[:-1])):
+            raise RuntimeError(f"cal_score: {name} must be uint8 {tuple(p.shape[:-1])}, got {t.dtype} {tuple(t.shape)}")
+    u_scale = 0.0
+    if unc is not None:
+        if unc.dtype != torch.float32 or tuple(unc.shape) != tuple(p.shape[:-1]):
+            raise RuntimeError(f"cal_score: unc must be fp32 {tuple(p.shape[:-1])}, got {unc.dtype} {tuple(unc.shape)}")
+        if u_max is None:
+            raise RuntimeError("cal_score: unc needs u_max, the value at the upper end of its last bin")
+        from ..calibration import u_scale as cal_u_scale                   # (the one definition; ValueError for a bad u_max)
+        u_scale = float(cal_u_scale(M, u_max))
+    if out is None:
+        out = torch.empty((B, slots), dtype=torch.int64, device=p.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (B, slots) or out.data_ptr() % 8:
+        raise RuntimeError(f"cal_score: out must be int64 {(B, slots)}, 8-byte aligned, got {out.dtype} {tuple(out.shape)}")
+    L.check(L.load().m1_cal_score(_p(p), _dt(p), _p(label), _p(mask), _p(unc), u_scale, B, V, K, M, _p(out), _stream()), "m1_cal_score")
+    return out
+
+
+def read_cal_records(records: torch.Tensor, K: int, bins: int) -> list:
+    """The records of ``cal_score`` ((N, slots); several batches concatenated) on the host, one dict per case (synchronises): "K",
+    "M", the ints n_valid / n_invalid / n_ignored / nll, and uint64 arrays brier (K,), top_count / top_conf_sum / top_correct (M,),
+    cls_count / cls_p_sum / cls_pos (K, M), unc_count / unc_u_sum / unc_errors (M,) -- the layout calibration.reliability_host
+    returns."""
+    K, M = int(K), int(bins)
+    slots = cal_record_slots(K, M)
+    w = records.detach().reshape(-1, slots).cpu().numpy().view("uint64")
+    out = []
+    for r in w:
+        d = {"K": K, "M": M}
+        d.update({k: int(r[i]) for i, k in enumerate(L.CAL_HEAD_KEYS)})
+        d["brier"] = r[4:4 + K].copy()
+        h = r[L.M1_CAL_HEAD:].reshape(K + 2, 3, M)
+        for j, k in enumerate(L.CAL_HIST_KEYS["top"]):
+            d["top_" + k] = h[0, j].copy()
+        for j, k in enumerate(L.CAL_HIST_KEYS["cls"]):
+            d["cls_" + k] = h[1:K + 1, j].copy()
+        for j, k in enumerate(L.CAL_HIST_KEYS["unc"]):
+            d["unc_" + k] = h[K + 1, j].copy()
+        out.append(d)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Focal loss on the softmax heads (losses.py:32-49)
 # ---------------------------------------------------------------------------------------------------------
 class _Focal(torch.autograd.Function):

@@ -34,7 +34,11 @@ What differs from the reference, and why (its harness bugs a
     ``VALID_XLSX_PREFIX<fold>.xlsx`` with ``--DATA_FEED sheet`` (``device_batches(mode='valid')``), else from ``--VALID_NPY_DIR`` or
     ``--SYNTHETIC_VALID_SAMPLES`` synthetic cases seeded apart from the training cases.  The validation loss is the detection term
     on the mean of the draws (no KL, no L2); validation does not move the model's dropout stream, so the weights of a run do not
-    depend on whether it validated.
+    depend on whether it validated.  ``--VALIDATE_CALIBRATION 1`` (default 0) adds the calibration of the same predictions
+    (``calibration.py``; ``--VALIDATE_BINS`` bins, default 15): ``val_ece``, ``val_mce``, ``val_brier``, ``val_nll``, ``val_ece_c1``
+    ('lesion') or ``val_cw_ece`` ('zonal'), ``val_unc_auroc`` and ``val_err@refer10`` / ``val_err@refer20``.  The flag ADDS COLUMNS
+    behind ``val_cases``, and ``validation.csv`` writes its header once: start a fold's file with the setting it will keep (a
+    resumed run that switches the flag appends rows that no longer match the header).
   * checkpoints are ``model_weights_NNN.npz`` (callbacks.py); the fold-finished test uses the intended file name
     (the reference formats a set literal into it, T:103).
   * guarded optimiser step (flags of this build, all off by default; the reference passes none of them to its Adam, T:120):
@@ -146,6 +150,9 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--VALIDATE', type=int, default=0, help="1: validate every VALIDATE_PER_N_EPOCHS epochs from VALIDATE_MIN_EPOCH on")
     prsr.add_argument('--VALIDATE_TTA', type=str, default=[], nargs='*',
                       help="mirrored views of the validation predictions: id, w, h, d, hw, ... (unets.networks.tta_views); none = off")
+    prsr.add_argument('--VALIDATE_CALIBRATION', type=int, default=0,
+                      help="1: validation also reports calibration (ECE, MCE, Brier, NLL, referral); adds columns to validation.csv")
+    prsr.add_argument('--VALIDATE_BINS', type=int, default=15, help="bins of the calibration histograms (1..64)")
     prsr.add_argument('--VALID_NPY_DIR', type=str, default=None, help="--DATA_FEED cases: directory of held-out image_*.npy / label_*.npy pairs")
     prsr.add_argument('--SYNTHETIC_VALID_SAMPLES', type=int, default=4, help="held-out synthetic cases per fold when no .npy directory is given")
     # This build's guarded optimiser step (optim.Adam): all off by default
@@ -163,6 +170,16 @@ def validate_tta(args) -> dict:
         return {}
     unets.networks.tta_views(views)
     return {"tta": views}
+
+
+def validate_calibration(args) -> dict:
+    """``{"calibration": True, "bins": M}`` of --VALIDATE_CALIBRATION / --VALIDATE_BINS for callbacks.Validate (its ``validate_kw``),
+    the bin count checked before the first epoch; ``{}`` when the flag is off: the callback is then built as it is without it."""
+    if not args.VALIDATE_CALIBRATION:
+        return {}
+    if not 1 <= args.VALIDATE_BINS <= 64:
+        raise ValueError(f"--VALIDATE_BINS must be in 1..64, got {args.VALIDATE_BINS}")
+    return {"calibration": True, "bins": int(args.VALIDATE_BINS)}
 
 
 def optimizer_kwargs(args) -> dict:
@@ -300,7 +317,7 @@ def build_callbacks(args, f: int, model, fold_dir: str, init_epoch: int, valid_f
                                 n_draws=args.UNET_PROBA_ITER, train_obj=args.TRAIN_OBJ,
                                 metrics_dir=os.path.join(args.METRICS_DIR + args.NAME, 'F' + str(f + 1)), init_epoch=init_epoch,
                                 rank=rank, world=world, alpha=list(args.FOCAL_LOSS_ALPHA), gamma=args.FOCAL_LOSS_GAMMA,
-                                **validate_tta(args)))
+                                **validate_tta(args), **validate_calibration(args)))
     return out
 
 

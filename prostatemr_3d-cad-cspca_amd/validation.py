@@ -18,11 +18,13 @@ Per-case definitions, all from the record (``score_host`` is their fp64 numpy re
 """
 from __future__ import annotations
 
+import math
 from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import calibration as _cal            # (validate() has a parameter named calibration)
 from . import detection, surface_distance
 from .hip import ops
 from .unets.networks import tta_views
@@ -30,6 +32,8 @@ from .unets.networks import tta_views
 K_EPSILON = 1e-7
 DEFAULT_SPACING = (3.0, 0.5, 0.5)            # mm in (D,H,W) order: the grid of the README's model
 FP_RATES = (0.5, 1.0, 2.0)
+REFERRALS = (0.10, 0.20)                     # val_err@refer10 / val_err@refer20: the error rate kept after referring that share
+CALIBRATION_MAPS = ("entropy", "mutual_info", "expected_entropy")
 
 
 # ---- the record on the host ---------------------------------------------------------------------------------------------------
@@ -118,13 +122,34 @@ def summarise(cases: Sequence[dict], train_obj: str, with_entropy: bool = True) 
             out[f"val_hd95_c{k}"] = _nanmean(c["hd95"][k - 1] for c in cases)
             out[f"val_assd_c{k}"] = _nanmean(c["assd"][k - 1] for c in cases)
     out["val_cases"] = len(cases)
+    if cases and all("calibration" in c for c in cases):
+        out.update(summarise_calibration([c["calibration"] for c in cases], train_obj))
+    return out
+
+
+def summarise_calibration(records: Sequence[dict], train_obj: str) -> dict:
+    """The calibration keys of ``summarise``, all from the POOLED record (``calibration.merge``: the voxels of every case together):
+    ECE and MCE of the arg-max label, the Brier score (summed over the classes) and the NLL per voxel, the one-vs-rest ECE of class 1
+    ('lesion') or the class-wise ECE ('zonal'), the AUROC of the uncertainty bin as a detector of wrong voxels and the error rate
+    kept after referring the most uncertain 10 % / 20 % of the voxels (NaN without an uncertainty map: one draw)."""
+    rec = _cal.merge(records)
+    out = {"val_ece": _cal.ece(rec), "val_mce": _cal.mce(rec), "val_brier": _cal.brier(rec)["total"],
+           "val_nll": _cal.nll(rec)}
+    if train_obj == "lesion":
+        out["val_ece_c1"] = _cal.classwise_ece(rec, (1,))
+    else:
+        out["val_cw_ece"] = _cal.classwise_ece(rec)
+    out["val_unc_auroc"] = _cal.uncertainty_auroc(rec)
+    curve = _cal.referral_curve(rec)
+    for x in REFERRALS:
+        out["val_err@refer%d" % round(100 * x)] = _cal.error_at_referral(curve, x)
     return out
 
 
 # ---- the pass ----------------------------------------------------------------------------------------------------------------------
 def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws_per_pass: int = 1,
              alpha: Sequence[float] = (0.25, 0.75), gamma: float = 2.0, spacing=None, rank: int = 0, world: int = 1,
-             tta=None) -> dict:
+             tta=None, calibration: bool = False, bins: int = 15, calibration_uncertainty: str = "entropy") -> dict:
     """``steps`` batches of ``batches`` (an iterator of ``({"image": x}, {"detection": y, ...})`` as the feeds yield them, y one-hot)
     through ``model.get_detect_model()`` -> the dict of ``summarise``.
 
@@ -140,6 +165,12 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
 
     The loss reported as ``val_focal`` is the detection term on the MC mean alone: no KL, no L2 (module docstring).
 
+    ``calibration`` (off by default: the calls and the keys are then exactly those above): one more launch pair per batch,
+    ``ops.cal_score`` on the mean and the arg-max labels with ``bins`` bins, and -- with more than one draw behind the mean -- on the
+    map ``calibration_uncertainty`` names ('entropy'; 'mutual_info' / 'expected_entropy' make the batch go through
+    ``predict_mc(..., uncertainty=True)``), binned up to ln K.  The records stay on the device and are read with the scoring records;
+    every case carries its own under "calibration", and ``summarise`` appends the keys of ``summarise_calibration``.
+
     Validation leaves no trace on training: the model's ``rng_state`` ({seed, step}) and its ``training`` flag are put back
     afterwards, whatever happens, so a run with validation gives the weights of the run without it bit for bit.
 
@@ -149,9 +180,13 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
         raise ValueError(f"train_obj must be 'zonal' or 'lesion', got {train_obj!r}")
     if model.references.cascaded != False:  # noqa: E712
         raise NotImplementedError("validate: a cascaded model returns two predictions per case; only the standalone model is scored")
+    if calibration_uncertainty not in CALIBRATION_MAPS:
+        raise ValueError(f"calibration_uncertainty must be one of {CALIBRATION_MAPS}, got {calibration_uncertainty!r}")
     n, steps = int(n_draws), int(steps)
     views = tta_views(tta)
     N = n * (len(views) if views else 1)                                   # draws behind one mean
+    cal_on, cal_recs, cal_map = bool(calibration), [], None
+    ukw = {"uncertainty": True} if cal_on and N > 1 and calibration_uncertainty != "entropy" else {}
     spacing = DEFAULT_SPACING if spacing is None else tuple(float(s) for s in spacing)
     saved_rng, was_training = model.rng_state.clone(), model.training
     detect = model.get_detect_model()
@@ -165,12 +200,12 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
                 y = by["detection"] if isinstance(by, dict) else by
                 y = y.contiguous()
                 if views is not None:
-                    o = detect.predict_mc(bx, n, draws_per_pass, tta=views)
+                    o = detect.predict_mc(bx, n, draws_per_pass, tta=views, **ukw)
                     mean, ent = o["mean"], (o["entropy"] if N > 1 else None)
                 elif n == 1:
                     mean, ent = detect.predict(bx), None
                 else:
-                    o = detect.predict_mc(bx, n, draws_per_pass)
+                    o = detect.predict_mc(bx, n, draws_per_pass, **ukw)
                     mean, ent = o["mean"], o["entropy"]
                 mean = mean.contiguous()
                 B, K = int(mean.shape[0]), int(mean.shape[-1])
@@ -180,6 +215,9 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
                 if ws is None or ws.numel() < need:                        # one workspace for every batch of the pass
                     ws = torch.empty(max(need, 8), dtype=torch.uint8, device=mean.device)
                 recs.append(ops.val_score(mean, y, ent, alpha, gamma, ws))
+                if cal_on:
+                    cal_map = None if N == 1 else o[calibration_uncertainty].contiguous()
+                    cal_recs.append(ops.cal_score(mean, y.argmax(dim=-1).to(torch.uint8), bins, None, cal_map, math.log(K)))
                 batch = [{"index": (step, rank * B + i)} for i in range(B)]
                 if train_obj == "lesion":
                     det_map = detection.extract_lesion_candidates(mean[..., 1].contiguous(), "dynamic")[0]
@@ -194,6 +232,9 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
             rows = ops.read_val_records(torch.cat(recs), K) if recs else []                # the one host read of the records
             for c, r in zip(cases, rows):
                 c["record"] = r
+            if cal_recs:
+                for c, r in zip(cases, ops.read_cal_records(torch.cat(cal_recs), K, bins)):
+                    c["calibration"] = r
             for first, m in surf:
                 t = {k: m[k].double().cpu().numpy() for k in ("dice", "hdq", "assd")}
                 for i in range(len(t["dice"])):
