@@ -4,8 +4,10 @@
 //   m1_mc_finish: mean = sum_p / n, entropy = -sum_c mean_c ln(mean_c)
 //   m1_mc_accum_u / m1_mc_finish_u: the same pass and the same finish with two more accumulators, sum_h (+)= sum_r H(p_r) and
 //   sum_pp (+)= sum_r p_r^2, from the probabilities already in registers -> expected entropy (aleatoric), mutual information
-//   (epistemic, entropy - expected entropy) and the per-class population variance.  The item functions are the ones below with
-//   U = true; U = false is the code of m1_mc_accum / m1_mc_finish, unchanged.
+//   (epistemic, entropy - expected entropy) and the per-class population variance.
+//   m1_mc_accum_v: either pass over replicas that are mirrored views (test-time augmentation, see the block further down).
+// There is one accumulate item, mc_accum_item<T, NC, G, U, V>, and one finish item, mc_finish_item<NC, G, U>: U adds the two extra
+// sums, V reads a replica's group at mirrored coordinates, and every entry point above is an instantiation of them.
 // Both stream: a thread owns G consecutive voxels (G*nc elements = nc 16-byte vectors of logits) through every replica, so the
 // replica sum lives in registers and nothing is exchanged between threads (no atomics, no LDS).  The voxels behind the last whole
 // group, and everything when a pointer or the replica stride is not 16-byte aligned, take the same code with G = 1.
@@ -67,28 +69,60 @@ __device__ __forceinline__ float mc_draw_entropy(const float* p) {
     return a;
 }
 
-// G voxels starting at element e0 of every replica (rstride elements apart).  U: also sum_h (one value per voxel, from voxel e0 / NC)
-// and sum_pp (laid out as sum_p), every sum in the same association: replicas in replica order, then old + acc.
-template <typename T, int NC, int G, bool U = false>
-__device__ __forceinline__ void mc_accum_item(const T* lg, long long rstride, int R, long long e0, float* sum_p, int accumulate,
-                                              float* samples, float* sum_h = nullptr, float* sum_pp = nullptr) {
+// The G voxels from voxel v0 on, through every replica (rstride elements apart).  U: also sum_h (one value per voxel) and sum_pp
+// (laid out as sum_p), every sum in the same association: replicas in replica order, then old + acc.
+// V: the voxels are those of a (B, D, H, W) grid and replica r is a view mirrored by bits [3r, 3r + 3) of `flips` (bit 0: W, bit 1:
+// H, bit 2: D), so its group is read at (b, d', h', w'), x' = extent - 1 - x where the bit is set.  That is all V changes: where
+// replica r's group is read.  The callers keep a group inside one W row (G divides W), where it is one contiguous run; with a W
+// mirror the run starts at W - G - w and its voxels are reversed in registers, the classes of a voxel staying in order.
+template <typename T, int NC, int G, bool U, bool V>
+__device__ __forceinline__ void mc_accum_item(const T* lg, long long rstride, int R, long long v0, float* sum_p, int accumulate,
+                                              float* samples, float* sum_h, float* sum_pp, unsigned long long flips = 0, int D = 0,
+                                              int H = 0, int W = 0) {
     constexpr int E = G * NC, LV = sizeof(T) == 2 ? 8 : 4;
     constexpr bool VEC = G > 1;
+    const long long e0 = v0 * NC;
+    long long b = 0;
+    int d = 0, h = 0, w = 0;
+    if constexpr (V) {                                                          // (v0 = ((b * D + d) * H + h) * W + w)
+        const long long row = v0 / W, bd = row / H;
+        w = (int)(v0 - row * W), h = (int)(row - bd * H);
+        b = bd / D;
+        d = (int)(bd - b * D);
+    }
     float old[E], acc[E];
     float oldq[U ? E : 1], accq[U ? E : 1], oldh[U ? G : 1], acch[U ? G : 1];
     if (accumulate) mc_ld<E, VEC>(sum_p + e0, old);
     if constexpr (U) {
         if (accumulate) {
             mc_ld<E, VEC>(sum_pp + e0, oldq);
-            mc_ld<G, VEC>(sum_h + e0 / NC, oldh);
+            mc_ld<G, VEC>(sum_h + v0, oldh);
         }
     }
     for (int r = 0; r < R; ++r) {
+        unsigned m = 0;
+        long long src = e0;                                                     // (where the group starts inside replica r)
+        if constexpr (V) {
+            m = (unsigned)(flips >> (3 * r)) & 7u;
+            const int ds = (m & 4u) ? D - 1 - d : d, hs = (m & 2u) ? H - 1 - h : h, ws = (m & 1u) ? W - G - w : w;
+            src = (((b * D + ds) * H + hs) * W + ws) * NC;
+        }
         float v[E];
-        const T* p = lg + (long long)r * rstride + e0;
+        const T* p = lg + (long long)r * rstride + src;
         if constexpr (VEC) {
 #pragma unroll
             for (int q = 0; q < E / LV; ++q) VecIO<T, LV>::ld(p + q * LV, v + q * LV);
+            if (m & 1u) {                                                       // (the run was read backwards: voxel g <-> G - 1 - g)
+#pragma unroll
+                for (int g = 0; g < G / 2; ++g) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        const float t = v[g * NC + c];
+                        v[g * NC + c] = v[(G - 1 - g) * NC + c];
+                        v[(G - 1 - g) * NC + c] = t;
+                    }
+                }
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < E; ++k) v[k] = Act<T>::ld(p + k);
@@ -104,21 +138,21 @@ __device__ __forceinline__ void mc_accum_item(const T* lg, long long rstride, in
             for (int k = 0; k < E; ++k) acc[k] = acc[k] + v[k];
         }
         if constexpr (U) {
-            float h[G];
+            float hh[G];
 #pragma unroll
-            for (int g = 0; g < G; ++g) h[g] = mc_draw_entropy<NC>(v + g * NC);
+            for (int g = 0; g < G; ++g) hh[g] = mc_draw_entropy<NC>(v + g * NC);
 #pragma unroll
             for (int k = 0; k < E; ++k) v[k] = v[k] * v[k];                  // (a rounded product: the file is not contracted)
             if (r == 0) {
 #pragma unroll
                 for (int k = 0; k < E; ++k) accq[k] = v[k];
 #pragma unroll
-                for (int g = 0; g < G; ++g) acch[g] = h[g];
+                for (int g = 0; g < G; ++g) acch[g] = hh[g];
             } else {
 #pragma unroll
                 for (int k = 0; k < E; ++k) accq[k] = accq[k] + v[k];
 #pragma unroll
-                for (int g = 0; g < G; ++g) acch[g] = acch[g] + h[g];
+                for (int g = 0; g < G; ++g) acch[g] = acch[g] + hh[g];
             }
         }
     }
@@ -135,38 +169,28 @@ __device__ __forceinline__ void mc_accum_item(const T* lg, long long rstride, in
             for (int g = 0; g < G; ++g) acch[g] = oldh[g] + acch[g];
         }
         mc_st<E, VEC>(sum_pp + e0, accq);
-        mc_st<G, VEC>(sum_h + e0 / NC, acch);
+        mc_st<G, VEC>(sum_h + v0, acch);
     }
 }
 
 // items [0, ngroups): whole groups of G voxels; items [ngroups, ngroups + ntail): the single voxels behind them.  M = B * V.
-template <typename T, int NC>
+// (sum_h and sum_pp are null without U)
+template <typename T, int NC, bool U>
 __global__ void __launch_bounds__(256) mc_accum_kernel(const T* __restrict__ lg, int R, long long M, long long ngroups,
-                                                       float* __restrict__ sum_p, int accumulate, float* __restrict__ samples) {
+                                                       float* __restrict__ sum_p, float* __restrict__ sum_h,
+                                                       float* __restrict__ sum_pp, int accumulate, float* __restrict__ samples) {
     constexpr int G = sizeof(T) == 2 ? 8 : 4;
     const long long items = ngroups + (M - ngroups * G), rstride = M * NC;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
-        if (i < ngroups) mc_accum_item<T, NC, G>(lg, rstride, R, i * (G * NC), sum_p, accumulate, samples);
-        else mc_accum_item<T, NC, 1>(lg, rstride, R, (ngroups * G + (i - ngroups)) * NC, sum_p, accumulate, samples);
+        if (i < ngroups) mc_accum_item<T, NC, G, U, false>(lg, rstride, R, i * G, sum_p, accumulate, samples, sum_h, sum_pp);
+        else mc_accum_item<T, NC, 1, U, false>(lg, rstride, R, ngroups * G + (i - ngroups), sum_p, accumulate, samples, sum_h, sum_pp);
     }
 }
 
-template <typename T, int NC>
-__global__ void __launch_bounds__(256) mc_accum_u_kernel(const T* __restrict__ lg, int R, long long M, long long ngroups,
-                                                         float* __restrict__ sum_p, float* __restrict__ sum_h,
-                                                         float* __restrict__ sum_pp, int accumulate, float* __restrict__ samples) {
-    constexpr int G = sizeof(T) == 2 ? 8 : 4;
-    const long long items = ngroups + (M - ngroups * G), rstride = M * NC;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
-        if (i < ngroups) mc_accum_item<T, NC, G, true>(lg, rstride, R, i * (G * NC), sum_p, accumulate, samples, sum_h, sum_pp);
-        else mc_accum_item<T, NC, 1, true>(lg, rstride, R, (ngroups * G + (i - ngroups)) * NC, sum_p, accumulate, samples, sum_h, sum_pp);
-    }
-}
-
-template <int NC, int G, bool U = false>
+template <int NC, int G, bool U>
 __device__ __forceinline__ void mc_finish_item(const float* sum_p, float n, long long v0, float* mean, float* entropy,
-                                               const float* sum_h = nullptr, const float* sum_pp = nullptr, float* expected = nullptr,
-                                               float* mutual = nullptr, float* variance = nullptr) {
+                                               const float* sum_h, const float* sum_pp, float* expected, float* mutual,
+                                               float* variance) {
     constexpr int E = G * NC;
     constexpr bool VEC = G > 1;
     float m[E], h[G];
@@ -209,245 +233,32 @@ __device__ __forceinline__ void mc_finish_item(const float* sum_p, float n, long
     }
 }
 
-// (mean may alias sum_p: a thread reads its own elements before it writes them, so no __restrict__ on either)
-template <int NC>
-__global__ void __launch_bounds__(256) mc_finish_kernel(const float* sum_p, float n, long long M, long long ngroups, float* mean,
-                                                        float* __restrict__ entropy) {
+// (mean / expected / variance may alias sum_p / sum_h / sum_pp: a thread reads its own elements before it writes them, so none of
+// the six is __restrict__; entropy and mutual alias nothing.  Without U only sum_p, mean and entropy are given.)
+template <int NC, bool U>
+__global__ void __launch_bounds__(256) mc_finish_kernel(const float* sum_p, const float* sum_h, const float* sum_pp, float n,
+                                                        long long M, long long ngroups, float* mean, float* __restrict__ entropy,
+                                                        float* expected, float* __restrict__ mutual, float* variance) {
     constexpr int G = 4;
     const long long items = ngroups + (M - ngroups * G);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
-        if (i < ngroups) mc_finish_item<NC, G>(sum_p, n, i * G, mean, entropy);
-        else mc_finish_item<NC, 1>(sum_p, n, ngroups * G + (i - ngroups), mean, entropy);
+        if (i < ngroups) mc_finish_item<NC, G, U>(sum_p, n, i * G, mean, entropy, sum_h, sum_pp, expected, mutual, variance);
+        else mc_finish_item<NC, 1, U>(sum_p, n, ngroups * G + (i - ngroups), mean, entropy, sum_h, sum_pp, expected, mutual, variance);
     }
-}
-
-// (mean / expected / variance may alias sum_p / sum_h / sum_pp, so none of the six is __restrict__; entropy and mutual alias nothing)
-template <int NC>
-__global__ void __launch_bounds__(256) mc_finish_u_kernel(const float* sum_p, const float* sum_h, const float* sum_pp, float n,
-                                                          long long M, long long ngroups, float* mean, float* __restrict__ entropy,
-                                                          float* expected, float* __restrict__ mutual, float* variance) {
-    constexpr int G = 4;
-    const long long items = ngroups + (M - ngroups * G);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
-        if (i < ngroups) mc_finish_item<NC, G, true>(sum_p, n, i * G, mean, entropy, sum_h, sum_pp, expected, mutual, variance);
-        else mc_finish_item<NC, 1, true>(sum_p, n, ngroups * G + (i - ngroups), mean, entropy, sum_h, sum_pp, expected, mutual, variance);
-    }
-}
-
-static inline bool mc_al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-template <typename T>
-static int mc_accum_launch(const void* logits, int R, long long M, int nc, float* sum_p, int accumulate, float* samples, hipStream_t st) {
-    constexpr int G = sizeof(T) == 2 ? 8 : 4;
-    const bool vec = mc_al(logits, 16) && mc_al(sum_p, 16) && (!samples || mc_al(samples, 16)) &&
-                     (R == 1 || (M * nc * (long long)sizeof(T)) % 16 == 0);
-    const long long ngroups = vec ? M / G : 0, items = ngroups + (M - ngroups * G);
-    const dim3 grid(m1_grid_for(items, 1)), block(256);
-    const int acc = accumulate != 0;
-    switch (nc) {
-        case 2: hipLaunchKernelGGL((mc_accum_kernel<T, 2>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, acc, samples); break;
-        case 3: hipLaunchKernelGGL((mc_accum_kernel<T, 3>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, acc, samples); break;
-        default: hipLaunchKernelGGL((mc_accum_kernel<T, 4>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, acc, samples); break;
-    }
-    return m1_check_launch();
-}
-
-extern "C" int m1_mc_accum(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, int accumulate,
-                           float* samples_out, void* stream) {
-    if (m1_debug_skip("mc_accum")) return M1_OK;
-    if (!logits || !sum_p || R <= 0 || B <= 0 || V <= 0 || (dtype != M1_F32 && dtype != M1_BF16)) return M1_ERR_BAD_ARG;
-    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
-    if (!mc_al(logits, dtype == M1_BF16 ? 2 : 4) || !mc_al(sum_p, 4) || !mc_al(samples_out, 4)) return M1_ERR_BAD_ARG;
-    const long long M = (long long)B * V;
-    if (M > (1ll << 40) / R) return M1_ERR_BAD_ARG;                   // (element offsets stay far inside 63 bits)
-    const double el = (double)M * nc;
-    M1ProfScope ps("mc_accum", 0.0, el * R * (dtype == M1_BF16 ? 2 : 4) + el * 4 * (accumulate ? 2 : 1) + (samples_out ? el * R * 4 : 0.0),
-                   (hipStream_t)stream);
-    return dtype == M1_BF16 ? mc_accum_launch<bf16_t>(logits, R, M, nc, sum_p, accumulate, samples_out, (hipStream_t)stream)
-                            : mc_accum_launch<float>(logits, R, M, nc, sum_p, accumulate, samples_out, (hipStream_t)stream);
-}
-
-extern "C" int m1_mc_finish(const float* sum_p, int n_draws, int B, long long V, int nc, float* mean, float* entropy, void* stream) {
-    if (m1_debug_skip("mc_finish")) return M1_OK;
-    if (!sum_p || !mean || !entropy || n_draws <= 0 || B <= 0 || V <= 0) return M1_ERR_BAD_ARG;
-    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
-    if (!mc_al(sum_p, 4) || !mc_al(mean, 4) || !mc_al(entropy, 4)) return M1_ERR_BAD_ARG;
-    const long long M = (long long)B * V;
-    if (M > (1ll << 40)) return M1_ERR_BAD_ARG;
-    const bool vec = mc_al(sum_p, 16) && mc_al(mean, 16) && mc_al(entropy, 16);
-    const long long ngroups = vec ? M / 4 : 0, items = ngroups + (M - ngroups * 4);
-    const dim3 grid(m1_grid_for(items, 1)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    M1ProfScope ps("mc_finish", 0.0, (double)M * (2.0 * nc + 1.0) * 4, st);
-    const float n = (float)n_draws;
-    switch (nc) {
-        case 2: hipLaunchKernelGGL(mc_finish_kernel<2>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
-        case 3: hipLaunchKernelGGL(mc_finish_kernel<3>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
-        default: hipLaunchKernelGGL(mc_finish_kernel<4>, grid, block, 0, st, sum_p, n, M, ngroups, mean, entropy); break;
-    }
-    return m1_check_launch();
-}
-
-template <typename T>
-static int mc_accum_u_launch(const void* logits, int R, long long M, int nc, float* sum_p, float* sum_h, float* sum_pp, int accumulate,
-                             float* samples, hipStream_t st) {
-    constexpr int G = sizeof(T) == 2 ? 8 : 4;
-    const bool vec = mc_al(logits, 16) && mc_al(sum_p, 16) && mc_al(sum_h, 16) && mc_al(sum_pp, 16) && (!samples || mc_al(samples, 16)) &&
-                     (R == 1 || (M * nc * (long long)sizeof(T)) % 16 == 0);
-    const long long ngroups = vec ? M / G : 0, items = ngroups + (M - ngroups * G);
-    const dim3 grid(m1_grid_for(items, 1)), block(256);
-    const int acc = accumulate != 0;
-    switch (nc) {
-        case 2: hipLaunchKernelGGL((mc_accum_u_kernel<T, 2>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, sum_h, sum_pp, acc, samples); break;
-        case 3: hipLaunchKernelGGL((mc_accum_u_kernel<T, 3>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, sum_h, sum_pp, acc, samples); break;
-        default: hipLaunchKernelGGL((mc_accum_u_kernel<T, 4>), grid, block, 0, st, (const T*)logits, R, M, ngroups, sum_p, sum_h, sum_pp, acc, samples); break;
-    }
-    return m1_check_launch();
-}
-
-extern "C" int m1_mc_accum_u(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, float* sum_h, float* sum_pp,
-                             int accumulate, float* samples_out, void* stream) {
-    if (m1_debug_skip("mc_accum")) return M1_OK;
-    if (!logits || !sum_p || !sum_h || !sum_pp || R <= 0 || B <= 0 || V <= 0 || (dtype != M1_F32 && dtype != M1_BF16)) return M1_ERR_BAD_ARG;
-    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
-    if (!mc_al(logits, dtype == M1_BF16 ? 2 : 4) || !mc_al(sum_p, 4) || !mc_al(sum_h, 4) || !mc_al(sum_pp, 4) || !mc_al(samples_out, 4))
-        return M1_ERR_BAD_ARG;
-    const long long M = (long long)B * V;
-    if (M > (1ll << 40) / R) return M1_ERR_BAD_ARG;                   // (element offsets stay far inside 63 bits)
-    const double el = (double)M * nc;
-    M1ProfScope ps("mc_accum_u", 0.0, el * R * (dtype == M1_BF16 ? 2 : 4) + (2.0 * el + (double)M) * 4 * (accumulate ? 2 : 1) +
-                   (samples_out ? el * R * 4 : 0.0), (hipStream_t)stream);
-    return dtype == M1_BF16 ? mc_accum_u_launch<bf16_t>(logits, R, M, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, (hipStream_t)stream)
-                            : mc_accum_u_launch<float>(logits, R, M, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, (hipStream_t)stream);
-}
-
-extern "C" int m1_mc_finish_u(const float* sum_p, const float* sum_h, const float* sum_pp, int n_draws, int B, long long V, int nc,
-                              float* mean, float* entropy, float* expected_entropy, float* mutual_info, float* variance, void* stream) {
-    if (m1_debug_skip("mc_finish")) return M1_OK;
-    if (!sum_p || !sum_h || !sum_pp || !mean || !entropy || !expected_entropy || !mutual_info || !variance || n_draws <= 0 || B <= 0 ||
-        V <= 0)
-        return M1_ERR_BAD_ARG;
-    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
-    const void* ptrs[8] = {sum_p, sum_h, sum_pp, mean, entropy, expected_entropy, mutual_info, variance};
-    bool vec = true;
-    for (const void* p : ptrs) {
-        if (!mc_al(p, 4)) return M1_ERR_BAD_ARG;
-        vec = vec && mc_al(p, 16);
-    }
-    const long long M = (long long)B * V;
-    if (M > (1ll << 40)) return M1_ERR_BAD_ARG;
-    const long long ngroups = vec ? M / 4 : 0, items = ngroups + (M - ngroups * 4);
-    const dim3 grid(m1_grid_for(items, 1)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    M1ProfScope ps("mc_finish_u", 0.0, (double)M * ((2.0 * nc + 1.0) + (2.0 * nc + 3.0)) * 4, st);      // (read sums, write five maps)
-    const float n = (float)n_draws;
-    switch (nc) {
-        case 2: hipLaunchKernelGGL(mc_finish_u_kernel<2>, grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected_entropy, mutual_info, variance); break;
-        case 3: hipLaunchKernelGGL(mc_finish_u_kernel<3>, grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected_entropy, mutual_info, variance); break;
-        default: hipLaunchKernelGGL(mc_finish_u_kernel<4>, grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected_entropy, mutual_info, variance); break;
-    }
-    return m1_check_launch();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Test-time augmentation by mirroring: a view is a replica whose logits are read at mirrored coordinates.
 //   m1_mc_accum_v: m1_mc_accum / m1_mc_accum_u over (B, D, H, W) with one 3-bit mirror mask per replica (bit 0: W, bit 1: H, bit 2:
 //   D; replica r owns bits [3r, 3r + 3) of `flips`, passed by value: no device table, no memcpy node).  Output voxel (b, d, h, w)
-//   takes replica r's voxel (b, d', h', w'), x' = extent - 1 - x where the bit is set.  The item below is mc_accum_item with that
-//   one change in where a replica's group is read: the same softmax, entropy and square per voxel, the same association, so the sums
-//   and the samples are those of the unmirrored entry points on logits un-mirrored beforehand, bit for bit.
+//   takes replica r's voxel (b, d', h', w').  It is mc_accum_item with V = true: the same softmax, entropy and square per voxel, the
+//   same association, so the sums and the samples are those of the unmirrored entry points on logits un-mirrored beforehand, bit
+//   for bit.
 //   m1_tta_views: the stacked input of such a pass, replica r = x mirrored by mask r, one launch.
-// A group of G voxels is read as one contiguous run only inside one W row, so the vector path needs W % G == 0 (and the 16-byte
-// alignment of the unmirrored launchers); with a W mirror the run starts at W - G - w and its voxels are reversed in registers, the
-// classes of a voxel staying in order.  Every other shape runs the same item with G = 1.
+// A group of G voxels is read as one contiguous run only inside one W row, so the vector path needs W % G == 0 on top of the
+// alignment the unmirrored launch asks for, and every other shape runs the item with G = 1.  One G per launch, not groups and a
+// tail in one kernel: the G = 1 launch then keeps the few registers of the scalar item.
 // ---------------------------------------------------------------------------------------------------------------------------------
-template <typename T, int NC, int G, bool U>
-__device__ __forceinline__ void mc_accum_v_item(const T* lg, long long rstride, int R, unsigned long long flips, long long v0, int D,
-                                                int H, int W, float* sum_p, int accumulate, float* samples, float* sum_h, float* sum_pp) {
-    constexpr int E = G * NC, LV = sizeof(T) == 2 ? 8 : 4;
-    constexpr bool VEC = G > 1;
-    const long long e0 = v0 * NC, row = v0 / W, bd = row / H;
-    const int w = (int)(v0 - row * W), h = (int)(row - bd * H);
-    const long long b = bd / D;
-    const int d = (int)(bd - b * D);
-    float old[E], acc[E];
-    float oldq[U ? E : 1], accq[U ? E : 1], oldh[U ? G : 1], acch[U ? G : 1];
-    if (accumulate) mc_ld<E, VEC>(sum_p + e0, old);
-    if constexpr (U) {
-        if (accumulate) {
-            mc_ld<E, VEC>(sum_pp + e0, oldq);
-            mc_ld<G, VEC>(sum_h + v0, oldh);
-        }
-    }
-    for (int r = 0; r < R; ++r) {
-        const unsigned m = (unsigned)(flips >> (3 * r)) & 7u;
-        const int ds = (m & 4u) ? D - 1 - d : d, hs = (m & 2u) ? H - 1 - h : h, ws = (m & 1u) ? W - G - w : w;
-        float v[E];
-        const T* p = lg + (long long)r * rstride + (((b * D + ds) * H + hs) * W + ws) * NC;
-        if constexpr (VEC) {
-#pragma unroll
-            for (int q = 0; q < E / LV; ++q) VecIO<T, LV>::ld(p + q * LV, v + q * LV);
-            if (m & 1u) {                                                        // (the run was read backwards: voxel g <-> G - 1 - g)
-#pragma unroll
-                for (int g = 0; g < G / 2; ++g) {
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        const float t = v[g * NC + c];
-                        v[g * NC + c] = v[(G - 1 - g) * NC + c];
-                        v[(G - 1 - g) * NC + c] = t;
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < E; ++k) v[k] = Act<T>::ld(p + k);
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) mc_softmax<NC>(v + g * NC);
-        if (samples) mc_st<E, VEC>(samples + (long long)r * rstride + e0, v);
-        if (r == 0) {
-#pragma unroll
-            for (int k = 0; k < E; ++k) acc[k] = v[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < E; ++k) acc[k] = acc[k] + v[k];
-        }
-        if constexpr (U) {
-            float hh[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) hh[g] = mc_draw_entropy<NC>(v + g * NC);
-#pragma unroll
-            for (int k = 0; k < E; ++k) v[k] = v[k] * v[k];
-            if (r == 0) {
-#pragma unroll
-                for (int k = 0; k < E; ++k) accq[k] = v[k];
-#pragma unroll
-                for (int g = 0; g < G; ++g) acch[g] = hh[g];
-            } else {
-#pragma unroll
-                for (int k = 0; k < E; ++k) accq[k] = accq[k] + v[k];
-#pragma unroll
-                for (int g = 0; g < G; ++g) acch[g] = acch[g] + hh[g];
-            }
-        }
-    }
-    if (accumulate) {
-#pragma unroll
-        for (int k = 0; k < E; ++k) acc[k] = old[k] + acc[k];
-    }
-    mc_st<E, VEC>(sum_p + e0, acc);
-    if constexpr (U) {
-        if (accumulate) {
-#pragma unroll
-            for (int k = 0; k < E; ++k) accq[k] = oldq[k] + accq[k];
-#pragma unroll
-            for (int g = 0; g < G; ++g) acch[g] = oldh[g] + acch[g];
-        }
-        mc_st<E, VEC>(sum_pp + e0, accq);
-        mc_st<G, VEC>(sum_h + v0, acch);
-    }
-}
-
 // M = B * D * H * W voxels in items of G: G divides W (the launcher's vector condition), so it divides M and no item leaves its row
 template <typename T, int NC, int G, bool U>
 __global__ void __launch_bounds__(256) mc_accum_v_kernel(const T* __restrict__ lg, int R, unsigned long long flips, long long M, int D,
@@ -455,30 +266,52 @@ __global__ void __launch_bounds__(256) mc_accum_v_kernel(const T* __restrict__ l
                                                          float* __restrict__ sum_pp, int accumulate, float* __restrict__ samples) {
     const long long items = M / G, rstride = M * NC;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256)
-        mc_accum_v_item<T, NC, G, U>(lg, rstride, R, flips, i * G, D, H, W, sum_p, accumulate, samples, sum_h, sum_pp);
+        mc_accum_item<T, NC, G, U, true>(lg, rstride, R, i * G, sum_p, accumulate, samples, sum_h, sum_pp, flips, D, H, W);
+}
+
+static inline bool mc_al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+// The two launch shapes of one pass; `vec`: groups of G voxels may be read and written as 16-byte vectors
+template <typename T, int NC, bool U>
+static void mc_accum_launch(const T* lg, int R, long long M, float* sum_p, float* sum_h, float* sum_pp, int acc, float* samples, bool vec,
+                            hipStream_t st) {
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;
+    const long long ngroups = vec ? M / G : 0, items = ngroups + (M - ngroups * G);
+    const dim3 grid(m1_grid_for(items, 1)), block(256);
+    hipLaunchKernelGGL((mc_accum_kernel<T, NC, U>), grid, block, 0, st, lg, R, M, ngroups, sum_p, sum_h, sum_pp, acc, samples);
 }
 
 template <typename T, int NC, bool U>
-static int mc_accum_v_launch_nc(const void* logits, int R, unsigned long long flips, long long M, int D, int H, int W, float* sum_p,
-                                float* sum_h, float* sum_pp, int accumulate, float* samples, hipStream_t st) {
+static void mc_accum_v_launch(const T* lg, int R, unsigned long long flips, long long M, int D, int H, int W, float* sum_p, float* sum_h,
+                              float* sum_pp, int acc, float* samples, bool vec, hipStream_t st) {
     constexpr int G = sizeof(T) == 2 ? 8 : 4;
-    const bool vec = W % G == 0 && mc_al(logits, 16) && mc_al(sum_p, 16) && mc_al(sum_h, 16) && mc_al(sum_pp, 16) &&
-                     (!samples || mc_al(samples, 16)) && (R == 1 || (M * NC * (long long)sizeof(T)) % 16 == 0);
-    const long long items = vec ? M / G : M;
-    const dim3 grid(m1_grid_for(items, 1)), block(256);
+    const dim3 grid(m1_grid_for(vec ? M / G : M, 1)), block(256);
+    if (vec) hipLaunchKernelGGL((mc_accum_v_kernel<T, NC, G, U>), grid, block, 0, st, lg, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, acc, samples);
+    else hipLaunchKernelGGL((mc_accum_v_kernel<T, NC, 1, U>), grid, block, 0, st, lg, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, acc, samples);
+}
+
+// W > 0: the mirrored shape over (D, H, W); W == 0: the plain one.  The vector path: every pointer that is given 16-byte aligned, and
+// the replica stride a multiple of 16 bytes when there is more than one replica; mirrored, also whole groups in a W row.
+template <typename T, int NC, bool U>
+static int mc_accum_launch_nc(const void* logits, int R, unsigned long long flips, long long M, int D, int H, int W, float* sum_p,
+                              float* sum_h, float* sum_pp, int accumulate, float* samples, hipStream_t st) {
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;
+    const bool vec = mc_al(logits, 16) && mc_al(sum_p, 16) && mc_al(sum_h, 16) && mc_al(sum_pp, 16) && mc_al(samples, 16) &&
+                     (R == 1 || (M * NC * (long long)sizeof(T)) % 16 == 0);
     const int acc = accumulate != 0;
-    if (vec) hipLaunchKernelGGL((mc_accum_v_kernel<T, NC, G, U>), grid, block, 0, st, (const T*)logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, acc, samples);
-    else hipLaunchKernelGGL((mc_accum_v_kernel<T, NC, 1, U>), grid, block, 0, st, (const T*)logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, acc, samples);
+    if (W > 0) mc_accum_v_launch<T, NC, U>((const T*)logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, acc, samples, vec && W % G == 0, st);
+    else mc_accum_launch<T, NC, U>((const T*)logits, R, M, sum_p, sum_h, sum_pp, acc, samples, vec, st);
     return m1_check_launch();
 }
 
+// the runtime nc as the template parameter NC (the check holds it to 2..4)
 template <typename T, bool U>
-static int mc_accum_v_launch(const void* logits, int R, unsigned long long flips, long long M, int D, int H, int W, int nc, float* sum_p,
+static int mc_accum_dispatch(int nc, const void* logits, int R, unsigned long long flips, long long M, int D, int H, int W, float* sum_p,
                              float* sum_h, float* sum_pp, int accumulate, float* samples, hipStream_t st) {
     switch (nc) {
-        case 2: return mc_accum_v_launch_nc<T, 2, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
-        case 3: return mc_accum_v_launch_nc<T, 3, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
-        default: return mc_accum_v_launch_nc<T, 4, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+        case 2: return mc_accum_launch_nc<T, 2, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+        case 3: return mc_accum_launch_nc<T, 3, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+        default: return mc_accum_launch_nc<T, 4, U>(logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
     }
 }
 
@@ -490,28 +323,101 @@ static int mc_views_check(int R, unsigned long long flips) {
     return M1_OK;
 }
 
+// What the three accumulate entry points refuse, in the order they refuse it.  `vox`: the voxels of one sample, a double because
+// D * H * W of three ints need not fit 63 bits; `views`: the replicas are mirrored views, R and `flips` answer to mc_views_check.
+// sum_h and sum_pp come together or not at all.
+static int mc_accum_check(const void* logits, int R, int B, double vox, int nc, int dtype, bool views, unsigned long long flips,
+                          const float* sum_p, const float* sum_h, const float* sum_pp, const float* samples) {
+    if (!logits || !sum_p || (sum_h == nullptr) != (sum_pp == nullptr) || R <= 0 || B <= 0 || !(vox > 0) ||
+        (dtype != M1_F32 && dtype != M1_BF16))
+        return M1_ERR_BAD_ARG;
+    if (const int rc = views ? mc_views_check(R, flips) : M1_OK) return rc;
+    if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
+    if (!mc_al(logits, dtype == M1_BF16 ? 2 : 4) || !mc_al(sum_p, 4) || !mc_al(sum_h, 4) || !mc_al(sum_pp, 4) || !mc_al(samples, 4))
+        return M1_ERR_BAD_ARG;
+    if ((double)B * vox > (double)((1ll << 40) / R)) return M1_ERR_BAD_ARG;         // (element offsets stay far inside 63 bits)
+    return M1_OK;
+}
+
+// One pass behind every m1_mc_accum*: the check, the profile scope `scope` and the launch.  D = H = W = 0 without views.
+static int mc_accum_run(const char* scope, const void* logits, int R, int B, double vox, int D, int H, int W, int nc, int dtype,
+                        unsigned long long flips, float* sum_p, float* sum_h, float* sum_pp, int accumulate, float* samples, void* stream) {
+    if (const int rc = mc_accum_check(logits, R, B, vox, nc, dtype, W > 0, flips, sum_p, sum_h, sum_pp, samples)) return rc;
+    const long long M = (long long)((double)B * vox);                                // (exact: the check holds it under 2^40)
+    const bool u = sum_h != nullptr;
+    const double el = (double)M * nc;
+    hipStream_t st = (hipStream_t)stream;
+    M1ProfScope ps(scope, 0.0, el * R * (dtype == M1_BF16 ? 2 : 4) + (u ? 2.0 * el + (double)M : el) * 4 * (accumulate ? 2 : 1) +
+                   (samples ? el * R * 4 : 0.0), st);
+    if (dtype == M1_BF16)
+        return u ? mc_accum_dispatch<bf16_t, true>(nc, logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st)
+                 : mc_accum_dispatch<bf16_t, false>(nc, logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+    return u ? mc_accum_dispatch<float, true>(nc, logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st)
+             : mc_accum_dispatch<float, false>(nc, logits, R, flips, M, D, H, W, sum_p, sum_h, sum_pp, accumulate, samples, st);
+}
+
+extern "C" int m1_mc_accum(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, int accumulate,
+                           float* samples_out, void* stream) {
+    if (m1_debug_skip("mc_accum")) return M1_OK;
+    return mc_accum_run("mc_accum", logits, R, B, (double)V, 0, 0, 0, nc, dtype, 0ull, sum_p, nullptr, nullptr, accumulate, samples_out,
+                        stream);
+}
+
+extern "C" int m1_mc_accum_u(const void* logits, int R, int B, long long V, int nc, int dtype, float* sum_p, float* sum_h, float* sum_pp,
+                             int accumulate, float* samples_out, void* stream) {
+    if (m1_debug_skip("mc_accum")) return M1_OK;
+    if (!sum_h || !sum_pp) return M1_ERR_BAD_ARG;
+    return mc_accum_run("mc_accum_u", logits, R, B, (double)V, 0, 0, 0, nc, dtype, 0ull, sum_p, sum_h, sum_pp, accumulate, samples_out,
+                        stream);
+}
+
 extern "C" int m1_mc_accum_v(const void* logits, int R, int B, int D, int H, int W, int nc, int dtype, unsigned long long flips,
                              float* sum_p, float* sum_h, float* sum_pp, int accumulate, float* samples_out, void* stream) {
     if (m1_debug_skip("mc_accum")) return M1_OK;
-    if (!logits || !sum_p || (sum_h == nullptr) != (sum_pp == nullptr) || B <= 0 || D <= 0 || H <= 0 || W <= 0 ||
-        (dtype != M1_F32 && dtype != M1_BF16))
-        return M1_ERR_BAD_ARG;
-    if (const int rc = mc_views_check(R, flips)) return rc;
+    if (D <= 0 || H <= 0 || W <= 0) return M1_ERR_BAD_ARG;
+    return mc_accum_run("mc_accum_v", logits, R, B, (double)D * H * W, D, H, W, nc, dtype, flips, sum_p, sum_h, sum_pp, accumulate,
+                        samples_out, stream);
+}
+
+// Both finishes: U = false takes sum_p, mean and entropy alone and leaves the other five pointers null
+template <bool U>
+static int mc_finish_run(const char* scope, const float* sum_p, const float* sum_h, const float* sum_pp, int n_draws, int B, long long V,
+                         int nc, float* mean, float* entropy, float* expected, float* mutual, float* variance, void* stream) {
+    if (m1_debug_skip("mc_finish")) return M1_OK;
+    const void* ptrs[8] = {sum_p, mean, entropy, sum_h, sum_pp, expected, mutual, variance};
+    constexpr int np = U ? 8 : 3;
+    for (int i = 0; i < np; ++i)
+        if (!ptrs[i]) return M1_ERR_BAD_ARG;
+    if (n_draws <= 0 || B <= 0 || V <= 0) return M1_ERR_BAD_ARG;
     if (nc < 2 || nc > 4) return M1_ERR_UNSUPPORTED;
-    if (!mc_al(logits, dtype == M1_BF16 ? 2 : 4) || !mc_al(sum_p, 4) || !mc_al(sum_h, 4) || !mc_al(sum_pp, 4) || !mc_al(samples_out, 4))
-        return M1_ERR_BAD_ARG;
-    if ((double)B * D * H * W > (double)((1ll << 40) / R)) return M1_ERR_BAD_ARG;   // (element offsets stay far inside 63 bits)
-    const long long M = (long long)B * D * H * W;
-    const bool u = sum_h != nullptr;
-    const double el = (double)M * nc;
-    M1ProfScope ps("mc_accum_v", 0.0, el * R * (dtype == M1_BF16 ? 2 : 4) + (u ? 2.0 * el + (double)M : el) * 4 * (accumulate ? 2 : 1) +
-                   (samples_out ? el * R * 4 : 0.0), (hipStream_t)stream);
+    bool vec = true;
+    for (int i = 0; i < np; ++i) {
+        if (!mc_al(ptrs[i], 4)) return M1_ERR_BAD_ARG;
+        vec = vec && mc_al(ptrs[i], 16);
+    }
+    const long long M = (long long)B * V;
+    if (M > (1ll << 40)) return M1_ERR_BAD_ARG;
+    const long long ngroups = vec ? M / 4 : 0, items = ngroups + (M - ngroups * 4);
+    const dim3 grid(m1_grid_for(items, 1)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == M1_BF16)
-        return u ? mc_accum_v_launch<bf16_t, true>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st)
-                 : mc_accum_v_launch<bf16_t, false>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st);
-    return u ? mc_accum_v_launch<float, true>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st)
-             : mc_accum_v_launch<float, false>(logits, R, flips, M, D, H, W, nc, sum_p, sum_h, sum_pp, accumulate, samples_out, st);
+    M1ProfScope ps(scope, 0.0, (double)M * ((2.0 * nc + 1.0) + (U ? 2.0 * nc + 3.0 : 0.0)) * 4, st);    // (U: read the sums, write five maps)
+    const float n = (float)n_draws;
+    switch (nc) {
+        case 2: hipLaunchKernelGGL((mc_finish_kernel<2, U>), grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected, mutual, variance); break;
+        case 3: hipLaunchKernelGGL((mc_finish_kernel<3, U>), grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected, mutual, variance); break;
+        default: hipLaunchKernelGGL((mc_finish_kernel<4, U>), grid, block, 0, st, sum_p, sum_h, sum_pp, n, M, ngroups, mean, entropy, expected, mutual, variance); break;
+    }
+    return m1_check_launch();
+}
+
+extern "C" int m1_mc_finish(const float* sum_p, int n_draws, int B, long long V, int nc, float* mean, float* entropy, void* stream) {
+    return mc_finish_run<false>("mc_finish", sum_p, nullptr, nullptr, n_draws, B, V, nc, mean, entropy, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int m1_mc_finish_u(const float* sum_p, const float* sum_h, const float* sum_pp, int n_draws, int B, long long V, int nc,
+                              float* mean, float* entropy, float* expected_entropy, float* mutual_info, float* variance, void* stream) {
+    return mc_finish_run<true>("mc_finish_u", sum_p, sum_h, sum_pp, n_draws, B, V, nc, mean, entropy, expected_entropy, mutual_info,
+                               variance, stream);
 }
 
 // The copy in 16-byte chunks of a W row (W * C elements, a whole number of chunks; ET = the element as an unsigned integer): a thread

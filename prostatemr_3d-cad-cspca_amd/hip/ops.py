@@ -849,49 +849,89 @@ def _no_grad_only(what: str) -> None:
         raise RuntimeError(f"{what} is an inference op without a backward: call it under torch.no_grad()")
 
 
+def _mc_accum(what: str, logits: torch.Tensor, R: int, acc, samples, uncertainty: bool, views):
+    """The one body of ``mc_accum`` / ``mc_accum_u`` / ``mc_accum_v`` / ``mc_accumulate``, which document it; ``what`` names the caller
+    in the error messages.  ``acc``: the sum_p tensor, or the triple with ``uncertainty``."""
+    _no_grad_only(what)
+    R, ls = int(R), logits.shape
+    if views is None:
+        if len(ls) < 3 or R < 1 or ls[0] % R:
+            raise RuntimeError(f"{what}: logits {tuple(ls)} do not hold {R} replicas of a batch")
+    else:
+        if len(ls) != 5 or R < 1 or ls[0] % R:
+            raise RuntimeError(f"{what}: logits {tuple(ls)} are not (R*B, D, H, W, nc) with R = {R}")
+        R, flips = _flips(what, views, R)
+    B, nc = ls[0] // R, ls[-1]
+    shape = (B, *ls[1:])
+    shapes = (shape, shape[:-1], shape) if uncertainty else (shape,)
+    if acc is None:
+        add, sums = 0, ()
+    else:
+        add, sums = 1, (tuple(acc) if uncertainty else (acc,))
+        if len(sums) != len(shapes):
+            raise RuntimeError(f"{what}: acc must be (sum_p, sum_h, sum_pp), got {len(sums)} tensors")
+        for t, s, n in zip(sums, shapes, ("sum_p", "sum_h", "sum_pp")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != s:
+                raise RuntimeError(f"{what}: {n} must be fp32 {s}, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    draws = samples if isinstance(samples, torch.Tensor) else None     # (the caller's own slice of an (n_draws, B, ...) tensor)
+    if draws is not None and (draws.dtype != torch.float32 or draws.shape != (R, *shape)):
+        raise RuntimeError(f"{what}: samples must be fp32 {(R, *shape)}, got {draws.dtype} {tuple(draws.shape)}")
+    _req(logits, draws, *sums)
+    if not add:
+        sums = tuple([torch.empty(s, dtype=torch.float32, device=logits.device) for s in shapes])
+    if draws is None and samples:
+        draws = torch.empty((R, *shape), dtype=torch.float32, device=logits.device)
+    lib, lp, dt, dp, st = L.load(), logits.data_ptr(), _dt(logits), _p(draws), _stream()
+    sp, sh, sq = (t.data_ptr() for t in sums) if uncertainty else (sums[0].data_ptr(), None, None)
+    V = logits.numel() // (R * B * nc)
+    if views is not None:
+        L.check(lib.m1_mc_accum_v(lp, R, *shape, dt, flips, sp, sh, sq, add, dp, st), "m1_mc_accum_v")
+    elif uncertainty:
+        L.check(lib.m1_mc_accum_u(lp, R, B, V, nc, dt, sp, sh, sq, add, dp, st), "m1_mc_accum_u")
+    else:
+        L.check(lib.m1_mc_accum(lp, R, B, V, nc, dt, sp, add, dp, st), "m1_mc_accum")
+    res = sums if uncertainty else sums[0]
+    return res if draws is None else (res, draws)
+
+
+def _mc_finish(what: str, acc, n: int, uncertainty: bool):
+    """The one body of ``mc_finish`` / ``mc_finish_u`` / ``mc_finalize``: the dict of maps, each written over its accumulator."""
+    _no_grad_only(what)
+    sums = tuple(acc) if uncertainty else (acc,)
+    if uncertainty and len(sums) != 3:
+        raise RuntimeError(f"{what}: acc must be (sum_p, sum_h, sum_pp), got {len(sums)} tensors")
+    _req(*sums)
+    sum_p, ps = sums[0], sums[0].shape
+    if ([t for t in sums if t.dtype != torch.float32] or len(ps) < 2 or int(n) < 1
+            or (uncertainty and (sums[2].shape != ps or sums[1].shape != ps[:-1]))):
+        raise RuntimeError(f"{what}: acc must hold the fp32 accumulators of mc_accum{'_u' if uncertainty else ''} and n >= 1")
+    B, nc = ps[0], ps[-1]
+    V = sum_p.numel() // (B * nc)
+    ent = torch.empty(ps[:-1], dtype=torch.float32, device=sum_p.device)
+    if not uncertainty:
+        L.check(L.load().m1_mc_finish(_p(sum_p), int(n), B, V, nc, _p(sum_p), _p(ent), _stream()), "m1_mc_finish")
+        return {"mean": sum_p, "entropy": ent}
+    _, sum_h, sum_pp = sums
+    mi = torch.empty_like(ent)
+    L.check(L.load().m1_mc_finish_u(_p(sum_p), _p(sum_h), _p(sum_pp), int(n), B, V, nc, _p(sum_p), _p(ent), _p(sum_h), _p(mi), _p(sum_pp),
+                                    _stream()), "m1_mc_finish_u")
+    return {"mean": sum_p, "entropy": ent, "expected_entropy": sum_h, "mutual_info": mi, "variance": sum_pp}
+
+
 def mc_accum(logits: torch.Tensor, R: int, sum_p: Optional[torch.Tensor] = None, samples: bool = False):
     """One pass of an n-draw inference (m1_mc_accum): ``logits`` (R*B, D, H, W, nc) is the head's raw output over ``R`` replicas of
     the caller's B samples, replica-major.  ``sum_p=None`` starts an accumulator (B, D, H, W, nc) fp32 = sum_r softmax(logits_r) --
     written, not added to, so it needs no zero fill; a given ``sum_p`` is added to in place.  Returns ``sum_p``, or
     ``(sum_p, per-draw probabilities (R, B, D, H, W, nc) fp32)`` with ``samples=True`` or with ``samples`` = the fp32 tensor of that
     shape to write them into."""
-    _no_grad_only("mc_accum")
-    _req(logits, sum_p)
-    R = int(R)
-    if logits.dim() < 3 or R < 1 or int(logits.shape[0]) % R:
-        raise RuntimeError(f"mc_accum: logits {tuple(logits.shape)} do not hold {R} replicas of a batch")
-    B, nc = int(logits.shape[0]) // R, int(logits.shape[-1])
-    shape = (B, *logits.shape[1:])
-    V = logits.numel() // (R * B * nc)
-    if sum_p is None:
-        acc, sum_p = 0, torch.empty(shape, dtype=torch.float32, device=logits.device)
-    elif sum_p.dtype != torch.float32 or tuple(sum_p.shape) != shape:
-        raise RuntimeError(f"mc_accum: sum_p must be fp32 {shape}, got {sum_p.dtype} {tuple(sum_p.shape)}")
-    else:
-        acc = 1
-    draws = None
-    if isinstance(samples, torch.Tensor):                  # (the caller's own slice of an (n_draws, B, ...) tensor)
-        draws = samples
-        _req(draws)
-        if draws.dtype != torch.float32 or tuple(draws.shape) != (R, *shape):
-            raise RuntimeError(f"mc_accum: samples must be fp32 {(R, *shape)}, got {draws.dtype} {tuple(draws.shape)}")
-    elif samples:
-        draws = torch.empty((R, *shape), dtype=torch.float32, device=logits.device)
-    L.check(L.load().m1_mc_accum(_p(logits), R, B, V, nc, _dt(logits), _p(sum_p), acc, _p(draws), _stream()), "m1_mc_accum")
-    return sum_p if draws is None else (sum_p, draws)
+    return _mc_accum("mc_accum", logits, R, sum_p, samples, False, None)
 
 
 def mc_finish(sum_p: torch.Tensor, n: int):
     """(mean, entropy) of ``n`` accumulated draws (m1_mc_finish): mean = sum_p / n, written over ``sum_p``; entropy (B, D, H, W) fp32 =
     -sum_c mean_c ln(mean_c) in nats (scipy.stats.entropy's default), 0 ln 0 = 0."""
-    _no_grad_only("mc_finish")
-    _req(sum_p)
-    if sum_p.dtype != torch.float32 or sum_p.dim() < 2 or int(n) < 1:
-        raise RuntimeError("mc_finish: sum_p must be the fp32 accumulator of mc_accum and n >= 1")
-    B, nc = int(sum_p.shape[0]), int(sum_p.shape[-1])
-    ent = torch.empty(sum_p.shape[:-1], dtype=torch.float32, device=sum_p.device)
-    L.check(L.load().m1_mc_finish(_p(sum_p), int(n), B, sum_p.numel() // (B * nc), nc, _p(sum_p), _p(ent), _stream()), "m1_mc_finish")
-    return sum_p, ent
+    d = _mc_finish("mc_finish", sum_p, n, False)
+    return d["mean"], d["entropy"]
 
 
 def mc_accum_u(logits: torch.Tensor, R: int, acc=None, samples: bool = False):
@@ -899,36 +939,7 @@ def mc_accum_u(logits: torch.Tensor, R: int, acc=None, samples: bool = False):
     sum_pp (B, D, H, W, nc)), all fp32; sum_h (+)= sum_r H(softmax(logits_r)), sum_pp (+)= sum_r softmax(logits_r)^2.  ``acc=None`` starts
     the triple -- written, not added to, so no zero fill; a given triple is added to in place.  Returns the triple, or ``(triple,
     per-draw probabilities)`` with ``samples`` as in ``mc_accum``.  sum_p and the samples are ``mc_accum``'s, bit for bit."""
-    _no_grad_only("mc_accum_u")
-    _req(logits)
-    R = int(R)
-    if logits.dim() < 3 or R < 1 or int(logits.shape[0]) % R:
-        raise RuntimeError(f"mc_accum_u: logits {tuple(logits.shape)} do not hold {R} replicas of a batch")
-    B, nc = int(logits.shape[0]) // R, int(logits.shape[-1])
-    shape = (B, *logits.shape[1:])
-    V = logits.numel() // (R * B * nc)
-    if acc is None:
-        add = 0
-        acc = tuple(torch.empty(s, dtype=torch.float32, device=logits.device) for s in (shape, shape[:-1], shape))
-    else:
-        add, acc = 1, tuple(acc)
-        if len(acc) != 3:
-            raise RuntimeError(f"mc_accum_u: acc must be (sum_p, sum_h, sum_pp), got {len(acc)} tensors")
-        _req(*acc)
-        for t, s, what in zip(acc, (shape, shape[:-1], shape), ("sum_p", "sum_h", "sum_pp")):
-            if t.dtype != torch.float32 or tuple(t.shape) != tuple(s):
-                raise RuntimeError(f"mc_accum_u: {what} must be fp32 {tuple(s)}, got {t.dtype} {tuple(t.shape)}")
-    draws = None
-    if isinstance(samples, torch.Tensor):
-        draws = samples
-        _req(draws)
-        if draws.dtype != torch.float32 or tuple(draws.shape) != (R, *shape):
-            raise RuntimeError(f"mc_accum_u: samples must be fp32 {(R, *shape)}, got {draws.dtype} {tuple(draws.shape)}")
-    elif samples:
-        draws = torch.empty((R, *shape), dtype=torch.float32, device=logits.device)
-    L.check(L.load().m1_mc_accum_u(_p(logits), R, B, V, nc, _dt(logits), _p(acc[0]), _p(acc[1]), _p(acc[2]), add, _p(draws), _stream()),
-            "m1_mc_accum_u")
-    return acc if draws is None else (acc, draws)
+    return _mc_accum("mc_accum_u", logits, R, acc, samples, True, None)
 
 
 def mc_finish_u(acc, n: int):
@@ -936,20 +947,7 @@ def mc_finish_u(acc, n: int):
     "expected_entropy" = sum_h / n (over sum_h), "mutual_info" = max(entropy - expected_entropy, 0), "variance" = max(sum_pp / n -
     mean^2, 0) (over sum_pp)}, nats, fp32.  mean and entropy are ``mc_finish``'s, bit for bit, unless a draw held a NaN: then every map
     of that voxel is NaN here, where ``mc_finish``'s entropy reads 0."""
-    _no_grad_only("mc_finish_u")
-    acc = tuple(acc)
-    if len(acc) != 3:
-        raise RuntimeError(f"mc_finish_u: acc must be (sum_p, sum_h, sum_pp), got {len(acc)} tensors")
-    sum_p, sum_h, sum_pp = acc
-    _req(sum_p, sum_h, sum_pp)
-    if (any(t.dtype != torch.float32 for t in acc) or sum_p.dim() < 2 or int(n) < 1 or sum_pp.shape != sum_p.shape
-            or tuple(sum_h.shape) != tuple(sum_p.shape[:-1])):
-        raise RuntimeError("mc_finish_u: acc must be the fp32 accumulators of mc_accum_u and n >= 1")
-    B, nc = int(sum_p.shape[0]), int(sum_p.shape[-1])
-    ent, mi = (torch.empty(sum_h.shape, dtype=torch.float32, device=sum_p.device) for _ in range(2))
-    L.check(L.load().m1_mc_finish_u(_p(sum_p), _p(sum_h), _p(sum_pp), int(n), B, sum_p.numel() // (B * nc), nc, _p(sum_p), _p(ent),
-                                    _p(sum_h), _p(mi), _p(sum_pp), _stream()), "m1_mc_finish_u")
-    return {"mean": sum_p, "entropy": ent, "expected_entropy": sum_h, "mutual_info": mi, "variance": sum_pp}
+    return _mc_finish("mc_finish_u", acc, n, True)
 
 
 def _flips(what: str, views, R: Optional[int] = None) -> Tuple[int, int]:
@@ -967,38 +965,19 @@ def mc_accum_v(logits: torch.Tensor, R: int, views, acc=None, samples: bool = Fa
     of a pass whose replica r was computed on the input mirrored by ``views[r]``, a mask 0..7 (bit 0: W, bit 1: H, bit 2: D): the
     logits (R*B, D, H, W, nc) are read at the mirrored coordinates, so the accumulators and the samples (R, B, D, H, W, nc) are on the
     caller's own grid (m1_mc_accum_v).  Equal, bit for bit, to the plain op on logits that were flipped back beforehand."""
-    what = "mc_accum_v"
-    _no_grad_only(what)
-    R = int(R)
-    if logits.dim() != 5 or R < 1 or int(logits.shape[0]) % R:
-        raise RuntimeError(f"{what}: logits {tuple(logits.shape)} are not (R*B, D, H, W, nc) with R = {R}")
-    R, flips = _flips(what, views, R)
-    B, (D, H, W, nc) = int(logits.shape[0]) // R, (int(v) for v in logits.shape[1:])
-    shape = (B, D, H, W, nc)
-    shapes = (shape, shape[:-1], shape) if uncertainty else (shape,)
-    names = ("sum_p", "sum_h", "sum_pp")
-    if acc is None:
-        add, sums = 0, None
-    else:
-        add, sums = 1, (tuple(acc) if uncertainty else (acc,))
-        if len(sums) != len(shapes) or not all(isinstance(t, torch.Tensor) for t in sums):
-            raise RuntimeError(f"{what}: acc must be " + ("(sum_p, sum_h, sum_pp)" if uncertainty else "the sum_p tensor"))
-        for t, s, n in zip(sums, shapes, names):
-            if t.dtype != torch.float32 or tuple(t.shape) != s:
-                raise RuntimeError(f"{what}: {n} must be fp32 {s}, got {t.dtype} {tuple(t.shape)}")
-    draws = samples if isinstance(samples, torch.Tensor) else None
-    if draws is not None and (draws.dtype != torch.float32 or tuple(draws.shape) != (R, *shape)):
-        raise RuntimeError(f"{what}: samples must be fp32 {(R, *shape)}, got {draws.dtype} {tuple(draws.shape)}")
-    _req(logits, draws, *(sums or ()))
-    if sums is None:
-        sums = tuple(torch.empty(s, dtype=torch.float32, device=logits.device) for s in shapes)
-    if draws is None and samples:
-        draws = torch.empty((R, *shape), dtype=torch.float32, device=logits.device)
-    sp, sh, sq = sums if uncertainty else (sums[0], None, None)
-    L.check(L.load().m1_mc_accum_v(_p(logits), R, B, D, H, W, nc, _dt(logits), flips, _p(sp), _p(sh), _p(sq), add, _p(draws), _stream()),
-            "m1_mc_accum_v")
-    res = sums if uncertainty else sums[0]
-    return res if draws is None else (res, draws)
+    return _mc_accum("mc_accum_v", logits, R, acc, samples, uncertainty, tuple(views))
+
+
+def mc_accumulate(logits: torch.Tensor, R: int, acc=None, samples: bool = False, uncertainty: bool = False, views=None):
+    """The three ops above in one spelling: ``mc_accum_v`` with ``views``, else ``mc_accum_u`` with ``uncertainty``, else ``mc_accum``
+    (``acc`` is then its sum_p) -- the same launch and the same bits as the op it stands for."""
+    return _mc_accum("mc_accumulate", logits, R, acc, samples, uncertainty, views)
+
+
+def mc_finalize(acc, n: int, uncertainty: bool = False):
+    """The finish of ``mc_accumulate``'s result, always a dict: ``mc_finish_u`` of the triple with ``uncertainty``, else ``mc_finish``
+    of the sum_p tensor as {"mean", "entropy"}."""
+    return _mc_finish("mc_finalize", acc, n, uncertainty)
 
 
 def tta_views(x: torch.Tensor, views) -> torch.Tensor:

@@ -938,20 +938,19 @@ class M1(LoadableModel):
             def _mc_passes(self, x, n, R, uncertainty=False, eps_p=None, carry=None, total=0, first=0, advance=True, views=None):
                 """``n // R`` passes of ``R`` replicas each, folded into the accumulators ``carry`` = (sums, draws) of an earlier call
                 (another model's, see ``Ensemble``) or into fresh ones; returns (sums, draws), one entry per stage.  sums[j] is
-                ops.mc_accum's sum_p, or ops.mc_accum_u's triple with ``uncertainty``.  ``total`` > 0 asks for the per-draw
+                ops.mc_accumulate's sum_p, or its triple with ``uncertainty``.  ``total`` > 0 asks for the per-draw
                 probabilities: draws[j] is (total, B, D, H, W, nc), and this call fills [first, first + n).  The {seed, step} state
                 advances once per pass unless ``advance`` is False.
                 ``views`` (mirror masks, ``tta_views``): len(views) * n draws, view-major, in (len(views) * n) // R passes of R
                 consecutive draws; a pass's input is ops.tta_views of its draws' masks (both stages of a cascaded model alike) and
-                its logits go through ops.mc_accum_v, which un-mirrors them; the call fills [first, first + len(views) * n)."""
+                its logits go to ops.mc_accumulate with these masks, which un-mirrors them; the call fills
+                [first, first + len(views) * n)."""
                 prob = outer.references.probabilistic
                 casc = outer.references.cascaded != False  # noqa: E712
-                rep = (lambda t: t.repeat(R, 1, 1, 1, 1)) if R > 1 else (lambda t: t)
-                accum = ops.mc_accum_u if uncertainty else ops.mc_accum
+                # (with views the stacks come from ops.tta_views, pass by pass)
+                rep = (lambda t: t.repeat(R, 1, 1, 1, 1)) if R > 1 and views is None else (lambda t: t)
                 sums, draws = carry if carry is not None else (None, None)
                 with torch.no_grad():
-                    if views is not None:                                  # (the stacks come from ops.tta_views, pass by pass)
-                        rep = lambda t: t  # noqa: E731
                     if casc:
                         x1, x2 = outer._cascade_inputs(x)
                         xin = (rep(outer._prep(x1, channels=outer.input_channels)), rep(outer._prep(x2, channels=outer.input_channels)))
@@ -959,12 +958,11 @@ class M1(LoadableModel):
                         xin = rep(outer._prep(x))
                     base, mirrored, passes = xin, {}, (n if views is None else len(views) * n) // R
                     for k in range(passes):
-                        if views is not None:
-                            masks = tuple(views[j // n] for j in range(k * R, (k + 1) * R))
+                        masks = None if views is None else tuple(views[j // n] for j in range(k * R, (k + 1) * R))
+                        if masks is not None:
                             if masks not in mirrored:
                                 mirrored[masks] = tuple(ops.tta_views(t, masks) for t in base) if casc else ops.tta_views(base, masks)
                             xin = mirrored[masks]
-                            accum = lambda l, r, acc, samples, mk=masks: ops.mc_accum_v(l, r, mk, acc, samples, uncertainty)  # noqa: E731
                         if casc:
                             outer._forward_cascaded(xin, eps_p=eps_p, with_infer=prob)
                             outs = outer._last_cascade
@@ -978,7 +976,7 @@ class M1(LoadableModel):
                                      for l in logits]
                         for j, l in enumerate(logits):
                             lo = first + k * R
-                            r = accum(l, R, sums[j], samples=draws[j][lo:lo + R] if total else False)
+                            r = ops.mc_accumulate(l, R, sums[j], draws[j][lo:lo + R] if total else False, uncertainty, masks)
                             sums[j] = r[0] if total else r
                         if advance:
                             outer.advance_rng()
@@ -1159,11 +1157,7 @@ def _mc_results(sums, draws, n, uncertainty):
     res = []
     with torch.no_grad():
         for j, s in enumerate(sums):
-            if uncertainty:
-                d = ops.mc_finish_u(s, n)
-            else:
-                mean, ent = ops.mc_finish(s, n)
-                d = {"mean": mean, "entropy": ent}
+            d = ops.mc_finalize(s, n, uncertainty)
             if draws is not None:
                 d["samples"] = draws[j]
             res.append(d)
