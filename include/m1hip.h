@@ -804,6 +804,53 @@ size_t m1_cal_record_slots(int K, int bins);
 int m1_cal_score(const void* p, int p_dtype, const unsigned char* label, const unsigned char* mask, const float* unc, float u_scale,
                  int B, long long voxels, int K, int bins, unsigned long long* records, void* stream);
 
+/* ---- Case-level bootstrap replicates (no reference counterpart; bootstrap.py: AUROC, AP, FROC sensitivities, per-case means) ----
+ * The table is sorted once on the host (bootstrap.pack); csrc/bootstrap.hip computes one replicate per workgroup of 256 threads from
+ * the case multiplicities w[N], which it keeps in LDS (N <= M1_BOOTSTRAP_MAX_CASES = 16384: 64 KiB).
+ *   cases, in ASCENDING score order: case_label[N] (uint8, non-zero: a positive case), case_group_end[N] (uint8, 1 on the last case of
+ *     a run of equal scores), case_lesions[N] (int32, the case's annotated lesions, missed ones included: the recall denominator)
+ *   events -- unmatched candidates and matched lesions with confidence > 0 -- in DESCENDING confidence order: ev_case[M] (int32, index
+ *     into the case order above), ev_tp[M] (uint8, non-zero: a matched lesion), ev_group_end[M] (uint8).  M = 0 is legal.
+ *   values (V, N) fp64 or NULL with V = 0: row v holds one scalar per case (case order above), NaN = the case has none.  V <= 16.
+ *   draw_perm[N] (int32) or NULL (identity): the case index, in the order above, behind every index a draw picks.  bootstrap.pack
+ *     maps the caller's ORIGINAL case order here, so that two tables of the same cases get the same resamples whatever their scores;
+ *     for the stratified draw (P >= 0) the P positive cases come first.  An entry outside [0, N) drops the draw.
+ * The draw (without `weights`): Philox4x32-10 under the key seed + M1_STREAM_BOOTSTRAP * 0x9E3779B97F4A7C15 (mod 2^64; the other
+ * consumers' ids -- dropout layers 1, 2, ..., the augmentation table 0xA06D + 2 * rank and noise 0xA06E + 2 * rank, the latent heads
+ * 0x4C415400 + 8 * core + level -- are given by their callers).  Draw j < N of replicate b reads word j & 3 of counter
+ * (b << 12) + (j >> 2) and picks draw_perm[(word * N) >> 32]; stratified (P >= 0): j < P picks draw_perm[(word * P) >> 32], j >= P
+ * picks draw_perm[P + ((word * (N - P)) >> 32)].  w[i] = how often case i was picked: a pure function of (seed, b).
+ * `weights` (n_boot, N) int32 or NULL: row b REPLACES the draw (case order above; values are clamped to [0, 65535]).
+ * Row b of out (n_boot, 2 + n_rates + V) fp64, with P_w / N_w / S_w = the weight of the positive / negative / all cases and
+ * L_w = sum of w * case_lesions:
+ *   [0] auroc = 2U / (2 * P_w * N_w), 2U = sum over the groups of equal scores of pos_g * (2 * neg_below + neg_g), all weighted 64-bit
+ *       integers, one fp64 division: Mann-Whitney with ties counting half.  NaN unless P_w > 0 and N_w > 0.
+ *   [1] ap = sum over the event groups k, in order, with tp_k > tp_{k-1} of ((double)tp_k / L_w - (double)tp_{k-1} / L_w)
+ *       * ((double)tp_k / (double)(tp_k + fp_k)); tp_k, fp_k = weighted counts down to the group's end.  NaN when L_w = 0.
+ *   [2 + r] sens@fp_rates[r] = tp_k / L_w at the last group end with (double)fp_k / (double)S_w <= fp_rates[r]; 0 without one;
+ *       NaN when L_w = 0.
+ *   [2 + n_rates + v] = sum of (double)w_i * values[v][i] over the cases with w_i > 0 and a value that is not NaN, divided by their
+ *       weight; NaN without one.
+ * The integers do not depend on any order; the AP sum and the value sums are fp64 folds in a fixed order (thread, wave, block): a row
+ * repeats bit for bit over runs, n_boot (row b of a longer call is row b of a shorter one) and pointer alignments.  One launch, no
+ * global workspace, no memset / memcpy node, no host read; fp_rates: HOST doubles, passed by value.
+ * NULL table / out / a required array, N < 1, M < 0, n_boot < 1, n_rates outside 0..8, V outside 0..16, P > N,
+ * a pointer not aligned to its element: M1_ERR_BAD_ARG; n_boot > 2^20 or N > 16384: M1_ERR_UNSUPPORTED; all before any launch. */
+#define M1_STREAM_BOOTSTRAP 0x424F4F54ull        /* "BOOT" */
+#define M1_BOOTSTRAP_MAX_CASES 16384
+#define M1_BOOTSTRAP_MAX_BOOT (1 << 20)
+#define M1_BOOTSTRAP_MAX_RATES 8
+#define M1_BOOTSTRAP_MAX_VALUES 16
+#define M1_BOOTSTRAP_CHUNK 1024                  /* cases / events per block-wide scan */
+typedef struct {
+    const unsigned char* case_label; const unsigned char* case_group_end; const int* case_lesions;
+    const int* ev_case; const unsigned char* ev_tp; const unsigned char* ev_group_end;
+    const double* values; const int* draw_perm;
+    int N, M, V, P;                              /* P < 0: the draw is not stratified */
+} m1_bootstrap_table_t;
+int m1_bootstrap_metrics(const m1_bootstrap_table_t* table, int n_boot, uint64_t seed, const int* weights, const double* fp_rates,
+                         int n_rates, double* out, void* stream);
+
 /* Deferred folds of the weight-gradient partial copies (no reference counterpart; the reference's tf.GradientTape sums weight
  * gradients inside each op).  m1_conv3d_wgrad / m1_convT3d_wgrad split the voxels over blocks, every block stores its partial
  * tile into a copy inside `ws`, and a fold kernel adds the copies into dw / db in a fixed order.  After m1_wgrad_defer(1) the

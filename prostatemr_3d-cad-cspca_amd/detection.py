@@ -376,6 +376,28 @@ def froc(per_case_lesion_results, thresholds=None) -> dict:
             "num_cases": len(cases)}
 
 
+def average_precision(per_case_lesion_results) -> float:
+    """Lesion-level average precision over the thresholds of ``froc`` (every distinct positive confidence, from the largest down):
+    AP = sum_k (R_k - R_{k-1}) * P_k with R_0 = 0, R_k = ``froc``'s ``sensitivity`` at threshold k -- missed lesions count in its
+    denominator and are detected at no threshold -- and P_k = TP_k / (TP_k + FP_k), TP_k the matched lesions and FP_k the unmatched
+    candidates with confidence >= the threshold.  NaN without lesions, 0 with lesions and no positive confidence.
+
+    This is this project's own definition, like ``froc`` (module docstring).  Pinned in tests/test_bootstrap_host.py: without missed
+    lesions it equals ``sklearn.metrics.average_precision_score(is_lesion, confidence)``; with m missed of L lesions it is (L - m) / L
+    times sklearn's value on the list without the missed ones."""
+    cases = [list(c) for c in per_case_lesion_results]
+    curve = froc(cases)
+    if not curve["num_lesions"]:
+        return float("nan")
+    thr = curve["thresholds"]
+    tp = np.array([c for case in cases for is_l, c, ov in case if is_l and ov > 0], np.float64)
+    fp = np.array([c for case in cases for is_l, c, ov in case if not is_l], np.float64)
+    hit = (tp[None, :] >= thr[:, None]).sum(axis=1).astype(np.float64)
+    false = (fp[None, :] >= thr[:, None]).sum(axis=1).astype(np.float64)
+    recall = np.concatenate([[0.0], curve["sensitivity"]])
+    return float(np.sum((recall[1:] - recall[:-1]) * (hit / (hit + false))))
+
+
 def auroc(case_labels, case_scores) -> float:
     """Area under the ROC curve by ranks (Mann-Whitney U / (positives * negatives)), tied scores counting half; fp64."""
     y = np.asarray(case_labels).reshape(-1) != 0

@@ -128,6 +128,18 @@ M1_CAL_HEAD, M1_CAL_MIN_K, M1_CAL_MAX_K, M1_CAL_MAX_BINS, M1_CAL_MAX_VOXELS = 8,
 CAL_HEAD_KEYS = ("n_valid", "n_invalid", "n_ignored", "nll")
 CAL_HIST_KEYS = {"top": ("count", "conf_sum", "correct"), "cls": ("count", "p_sum", "pos"), "unc": ("count", "u_sum", "errors")}
 
+# m1_bootstrap_metrics: the Philox stream id of the draw, the caps and the items per block-wide scan
+M1_STREAM_BOOTSTRAP = 0x424F4F54
+M1_BOOTSTRAP_MAX_CASES, M1_BOOTSTRAP_MAX_BOOT, M1_BOOTSTRAP_MAX_RATES, M1_BOOTSTRAP_MAX_VALUES = 16384, 1 << 20, 8, 16
+M1_BOOTSTRAP_CHUNK = 1024
+
+
+class m1_bootstrap_table_t(C.Structure):
+    """The packed table of m1_bootstrap_metrics (include/m1hip.h): device pointers and the four counts."""
+    _fields_ = [(n, C.c_void_p) for n in ("case_label", "case_group_end", "case_lesions", "ev_case", "ev_tp", "ev_group_end",
+                                          "values", "draw_perm")] + [(n, C.c_int) for n in ("N", "M", "V", "P")]
+
+
 # enum m1_label_objective / m1_feed_mode
 M1_LABEL_LESION, M1_LABEL_ZONAL = 0, 1
 M1_FEED_TRAIN, M1_FEED_VALID, M1_FEED_TEST = 0, 1, 2
@@ -246,6 +258,7 @@ SIGNATURES = {
     "m1_val_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(_f), _f, _i, _ll, _i, _vp, _vp, _sz, _vp]),
     "m1_cal_record_slots": (_sz, [_i, _i]),
     "m1_cal_score": (_i, [_vp, _i, _vp, _vp, _vp, _f, _i, _ll, _i, _i, _vp, _vp]),
+    "m1_bootstrap_metrics": (_i, [C.POINTER(m1_bootstrap_table_t), _i, _u64, _vp, C.POINTER(_d), _i, _vp, _vp]),
     "m1_wgrad_defer": (_i, [_i]),
     "m1_wgrad_fold_pending": (_i, [_vp]),
     "m1_wgrad_fold_drop": (_i, []),

@@ -1117,6 +1117,66 @@ def read_cal_records(records: torch.Tensor, K: int, bins: int) -> list:
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Case-level bootstrap replicates (bootstrap.hip; bootstrap.replicates)
+# ---------------------------------------------------------------------------------------------------------
+_BS_ARRAYS = (("case_label", torch.uint8, "N"), ("case_group_end", torch.uint8, "N"), ("case_lesions", torch.int32, "N"),
+              ("ev_case", torch.int32, "M"), ("ev_tp", torch.uint8, "M"), ("ev_group_end", torch.uint8, "M"))
+
+
+def bootstrap_metrics(table: dict, n_boot: int, seed: int = 0, stratified: bool = False, fp_rates: Sequence[float] = (0.5, 1.0, 2.0),
+                      weights: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``n_boot`` bootstrap replicates of [auroc, ap, sens@fp_rates..., mean of every value row] in one launch (m1_bootstrap_metrics,
+    include/m1hip.h) -> (n_boot, 2 + len(fp_rates) + V) fp64 on the device.  ``table``: device tensors in the packed order of
+    ``bootstrap.pack`` (``bootstrap.to_device`` makes them): case_label / case_group_end uint8 (N,), case_lesions int32 (N,), ev_case
+    int32 (M,), ev_tp / ev_group_end uint8 (M,), optionally values fp64 (V, N) -- one ROW per scalar --, case_rank int32 (N,) (the packed
+    position of every original case: what a draw's index goes through; absent = identity) and, for ``stratified``, strat_perm int32 (N,)
+    with the int ``P`` in its place.  ``weights``: int32 (n_boot, N) in the packed case order, replacing the draw.  Nothing
+    is read back and every argument is checked before the launch."""
+    _no_grad_only("bootstrap_metrics")
+    ts = {}
+    for name, dt, dim in _BS_ARRAYS:
+        t = table.get(name)
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1:
+            raise RuntimeError(f"bootstrap_metrics: table[{name!r}] must be a 1-d {dt} device tensor")
+        ts[name] = t
+    N, M = int(ts["case_label"].numel()), int(ts["ev_case"].numel())
+    for name, _, dim in _BS_ARRAYS:
+        if ts[name].numel() != (N if dim == "N" else M):
+            raise RuntimeError(f"bootstrap_metrics: table[{name!r}] holds {ts[name].numel()} entries, {dim} = {N if dim == 'N' else M} expected")
+    values, V = table.get("values"), 0
+    if values is not None and values.numel():
+        if values.dtype != torch.float64 or values.dim() != 2 or int(values.shape[1]) != N:
+            raise RuntimeError(f"bootstrap_metrics: table['values'] must be fp64 (V, {N}), got {values.dtype} {tuple(values.shape)}")
+        V = int(values.shape[0])
+    else:
+        values = None
+    perm, P = table.get("case_rank"), -1                                   # (None: the draw indexes the packed order itself)
+    if stratified:
+        perm, P = table.get("strat_perm"), int(table.get("P", -1))
+        if perm is None or not 0 <= P <= N:
+            raise RuntimeError("bootstrap_metrics: a stratified draw needs table['strat_perm'] and 0 <= table['P'] <= N")
+    if perm is not None and (not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or tuple(perm.shape) != (N,)):
+        raise RuntimeError(f"bootstrap_metrics: the draw's permutation must be int32 ({N},)")
+    n_boot, rates = int(n_boot), [float(x) for x in fp_rates]
+    if weights is not None and (weights.dtype != torch.int32 or tuple(weights.shape) != (n_boot, N)):
+        raise RuntimeError(f"bootstrap_metrics: weights must be int32 {(n_boot, N)}, got {weights.dtype} {tuple(weights.shape)}")
+    _req(*ts.values(), values, perm, weights, out)
+    S = 2 + len(rates) + V
+    if out is None:
+        out = torch.empty((max(n_boot, 0), S), dtype=torch.float64, device=ts["case_label"].device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (n_boot, S):
+        raise RuntimeError(f"bootstrap_metrics: out must be fp64 {(n_boot, S)}, got {out.dtype} {tuple(out.shape)}")
+    tb = L.m1_bootstrap_table_t()
+    for name in ts:
+        setattr(tb, name, ts[name].data_ptr() or None)
+    tb.values, tb.draw_perm = _p(values), _p(perm)
+    tb.N, tb.M, tb.V, tb.P = N, M, V, P
+    L.check(L.load().m1_bootstrap_metrics(C.byref(tb), n_boot, int(seed) & (2 ** 64 - 1), _p(weights), (C.c_double * max(len(rates), 1))(*rates),
+                                          len(rates), _p(out), _stream()), "m1_bootstrap_metrics")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Focal loss on the softmax heads (losses.py:32-49)
 # ---------------------------------------------------------------------------------------------------------
 class _Focal(torch.autograd.Function):

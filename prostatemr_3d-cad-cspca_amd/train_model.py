@@ -38,7 +38,10 @@ What differs from the reference, and why (its harness bugs a
     (``calibration.py``; ``--VALIDATE_BINS`` bins, default 15): ``val_ece``, ``val_mce``, ``val_brier``, ``val_nll``, ``val_ece_c1``
     ('lesion') or ``val_cw_ece`` ('zonal'), ``val_unc_auroc`` and ``val_err@refer10`` / ``val_err@refer20``.  The flag ADDS COLUMNS
     behind ``val_cases``, and ``validation.csv`` writes its header once: start a fold's file with the setting it will keep (a
-    resumed run that switches the flag appends rows that no longer match the header).
+    resumed run that switches the flag appends rows that no longer match the header).  ``--VALIDATE_BOOTSTRAP N`` (default 0)
+    follows the same rule: it adds ``val_ap`` and, from N case-level bootstrap replicates in one kernel launch (``bootstrap.py``;
+    ``--VALIDATE_BOOTSTRAP_SEED``, ``--VALIDATE_BOOTSTRAP_STRATIFIED``), the 95 % percentile bounds ``<key>_lo`` / ``<key>_hi`` of
+    ``val_auroc``, ``val_ap`` and ``val_sens@*fp`` ('lesion') or of ``val_dice_c*`` / ``val_hd95_c*`` / ``val_assd_c*`` ('zonal').
   * checkpoints are ``model_weights_NNN.npz`` (callbacks.py); the fold-finished test uses the intended file name
     (the reference formats a set literal into it, T:103).
   * guarded optimiser step (flags of this build, all off by default; the reference passes none of them to its Adam, T:120):
@@ -153,6 +156,11 @@ def build_parser() -> argparse.ArgumentParser:
     prsr.add_argument('--VALIDATE_CALIBRATION', type=int, default=0,
                       help="1: validation also reports calibration (ECE, MCE, Brier, NLL, referral); adds columns to validation.csv")
     prsr.add_argument('--VALIDATE_BINS', type=int, default=15, help="bins of the calibration histograms (1..64)")
+    prsr.add_argument('--VALIDATE_BOOTSTRAP', type=int, default=0,
+                      help="N > 0: validation also reports val_ap and case-level bootstrap bounds (<key>_lo / <key>_hi) from N replicates; "
+                           "adds columns to validation.csv")
+    prsr.add_argument('--VALIDATE_BOOTSTRAP_SEED', type=int, default=0, help="seed of the bootstrap draw")
+    prsr.add_argument('--VALIDATE_BOOTSTRAP_STRATIFIED', type=int, default=0, help="1: resample positive and negative cases apart")
     prsr.add_argument('--VALID_NPY_DIR', type=str, default=None, help="--DATA_FEED cases: directory of held-out image_*.npy / label_*.npy pairs")
     prsr.add_argument('--SYNTHETIC_VALID_SAMPLES', type=int, default=4, help="held-out synthetic cases per fold when no .npy directory is given")
     # This build's guarded optimiser step (optim.Adam): all off by default
@@ -180,6 +188,18 @@ def validate_calibration(args) -> dict:
     if not 1 <= args.VALIDATE_BINS <= 64:
         raise ValueError(f"--VALIDATE_BINS must be in 1..64, got {args.VALIDATE_BINS}")
     return {"calibration": True, "bins": int(args.VALIDATE_BINS)}
+
+
+def validate_bootstrap(args) -> dict:
+    """``{"bootstrap": N, "bootstrap_seed": s, "bootstrap_stratified": bool}`` of --VALIDATE_BOOTSTRAP and its two companions for
+    callbacks.Validate (its ``validate_kw``), the count checked before the first epoch; ``{}`` when the flag is 0: the callback is then
+    built as it is without it."""
+    from . import validation
+    n = validation.check_bootstrap(args.VALIDATE_BOOTSTRAP)
+    if not n:
+        return {}
+    return {"bootstrap": n, "bootstrap_seed": int(args.VALIDATE_BOOTSTRAP_SEED),
+            "bootstrap_stratified": bool(args.VALIDATE_BOOTSTRAP_STRATIFIED)}
 
 
 def optimizer_kwargs(args) -> dict:
@@ -317,7 +337,7 @@ def build_callbacks(args, f: int, model, fold_dir: str, init_epoch: int, valid_f
                                 n_draws=args.UNET_PROBA_ITER, train_obj=args.TRAIN_OBJ,
                                 metrics_dir=os.path.join(args.METRICS_DIR + args.NAME, 'F' + str(f + 1)), init_epoch=init_epoch,
                                 rank=rank, world=world, alpha=list(args.FOCAL_LOSS_ALPHA), gamma=args.FOCAL_LOSS_GAMMA,
-                                **validate_tta(args), **validate_calibration(args)))
+                                **validate_tta(args), **validate_calibration(args), **validate_bootstrap(args)))
     return out
 
 

@@ -24,6 +24,7 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import bootstrap as _boot             # (validate() has a parameter named bootstrap)
 from . import calibration as _cal            # (validate() has a parameter named calibration)
 from . import detection, surface_distance
 from .hip import ops
@@ -146,10 +147,45 @@ def summarise_calibration(records: Sequence[dict], train_obj: str) -> dict:
     return out
 
 
+def check_bootstrap(n_boot, level: float = 0.95) -> int:
+    """The replicate count of ``validate(bootstrap=...)`` as an int: 0 (off) .. 2^20, with 0 < level < 1; ValueError otherwise."""
+    n = int(n_boot)
+    if n != n_boot or not 0 <= n <= _boot.MAX_BOOT:
+        raise ValueError(f"bootstrap must be a whole number in 0..{_boot.MAX_BOOT} (0 = off), got {n_boot!r}")
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"bootstrap_level must lie strictly between 0 and 1, got {level!r}")
+    return n
+
+
+def summarise_bootstrap(cases: Sequence[dict], train_obj: str, n_boot: int, seed: int = 0, level: float = 0.95,
+                        stratified: bool = False, device=None) -> dict:
+    """The bootstrap keys of ``validate``: one ``bootstrap.pack`` of the per-case list, ONE call of ``bootstrap.replicates`` (the
+    kernel with a ``device``) and the percentile interval of every column.  'lesion': ``val_ap`` (the point estimate,
+    ``detection.average_precision``), then ``<key>_lo`` / ``<key>_hi`` for val_auroc, val_ap and every val_sens@<x>fp; 'zonal': the
+    same pair for every val_dice_c<k>, val_hd95_c<k> and val_assd_c<k>.  Bounds of a column without a finite replicate are NaN."""
+    out = {}
+    if train_obj == "lesion":
+        out["val_ap"] = detection.average_precision([c["lesion_results"] for c in cases])
+    table = _boot.pack(cases, train_obj, FP_RATES)
+    if train_obj == "lesion":
+        keys = ["val_auroc", "val_ap"] + ["val_sens@%gfp" % x for x in FP_RATES]
+    else:
+        keys = ["val_" + name for name in table["value_names"]]
+    if table["N"]:
+        lo, hi, _ = _boot.interval(_boot.replicates(table, n_boot, seed, stratified, device=device), level)
+    else:
+        lo = hi = np.full(len(_boot.columns(table)), np.nan)
+    first = 0 if train_obj == "lesion" else 2 + len(FP_RATES)
+    for j, k in enumerate(keys):
+        out[k + "_lo"], out[k + "_hi"] = float(lo[first + j]), float(hi[first + j])
+    return out
+
+
 # ---- the pass ----------------------------------------------------------------------------------------------------------------------
 def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws_per_pass: int = 1,
              alpha: Sequence[float] = (0.25, 0.75), gamma: float = 2.0, spacing=None, rank: int = 0, world: int = 1,
-             tta=None, calibration: bool = False, bins: int = 15, calibration_uncertainty: str = "entropy") -> dict:
+             tta=None, calibration: bool = False, bins: int = 15, calibration_uncertainty: str = "entropy", bootstrap: int = 0,
+             bootstrap_seed: int = 0, bootstrap_level: float = 0.95, bootstrap_stratified: bool = False) -> dict:
     """``steps`` batches of ``batches`` (an iterator of ``({"image": x}, {"detection": y, ...})`` as the feeds yield them, y one-hot)
     through ``model.get_detect_model()`` -> the dict of ``summarise``.
 
@@ -171,6 +207,11 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
     ``predict_mc(..., uncertainty=True)``), binned up to ln K.  The records stay on the device and are read with the scoring records;
     every case carries its own under "calibration", and ``summarise`` appends the keys of ``summarise_calibration``.
 
+    ``bootstrap`` = n > 0 (off by default: the calls and the keys are then exactly those above): after the last batch rank 0 packs the
+    gathered case list and makes ONE more call, ``ops.bootstrap_metrics`` with n case-level replicates under ``bootstrap_seed``
+    (``bootstrap_stratified``: positive and negative cases resampled apart), and appends the keys of ``summarise_bootstrap`` behind all
+    others: ``val_ap`` and the ``bootstrap_level`` percentile bounds ``<key>_lo`` / ``<key>_hi``.  The other ranks do nothing more.
+
     Validation leaves no trace on training: the model's ``rng_state`` ({seed, step}) and its ``training`` flag are put back
     afterwards, whatever happens, so a run with validation gives the weights of the run without it bit for bit.
 
@@ -182,6 +223,7 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
         raise NotImplementedError("validate: a cascaded model returns two predictions per case; only the standalone model is scored")
     if calibration_uncertainty not in CALIBRATION_MAPS:
         raise ValueError(f"calibration_uncertainty must be one of {CALIBRATION_MAPS}, got {calibration_uncertainty!r}")
+    n_boot = check_bootstrap(bootstrap, bootstrap_level)
     n, steps = int(n_draws), int(steps)
     views = tta_views(tta)
     N = n * (len(views) if views else 1)                                   # draws behind one mean
@@ -251,4 +293,8 @@ def validate(model, batches, steps: int, train_obj: str, n_draws: int = 1, draws
         if rank != 0:
             return {}
         cases = merge_case_records(gathered)
-    return summarise(cases, train_obj, with_entropy=N > 1)
+    out = summarise(cases, train_obj, with_entropy=N > 1)
+    if n_boot:
+        out.update(summarise_bootstrap(cases, train_obj, n_boot, bootstrap_seed, bootstrap_level, bootstrap_stratified,
+                                       device=next(model.parameters()).device))
+    return out
