@@ -150,6 +150,15 @@ int m1_debug_checksum(const void* p, long long nbytes, unsigned long long* slot,
  * log, clear it and switch logging on / off; mode < 0: return it only.  Off by default.  The op tests of the special kernels assert
  * on it: a shape the special kernel declines would otherwise compare the generic kernel with itself and stay green. */
 const char* m1_debug_kernels(int mode);
+/* Plan log: what stands behind the weight-gradient kernel names of the log above, as a ';'-separated list with the same `mode` argument
+ * (off by default, nothing recorded while off, valid until the next call):
+ *   wg:<kernel name> tiles=<K-tiles; voxels for wgrad_mfma> want=<splits asked of the copy planner> splits=<launched>
+ *      fit=<copies the region holds> rx=<0|1: partial copies + fold> stages=<S or 0> grid=<x,y,z>      every weight-gradient launcher
+ *   fold:<generic|vec|wide> copies=<n> n=<floats> nb=<bias floats> el=<EL> <queued|now>                 every fold of partial copies
+ *   foldbatch:n=<jobs> blocks=<total>                                                                   every batched fold launch
+ *   decline:<rung> rc=<code>      a rung of the weight-gradient ladder whose gate held returned M1_ERR_UNSUPPORTED / M1_ERR_WORKSPACE
+ *   stem:cp=<4|8>                 the padded stem path ran */
+const char* m1_debug_plans(int mode);
 int m1_debug_scribble(int blocks, int spins, void* stream);
 
 /* ---- Conv3DTranspose(padding='same') + bias : N:496-499,505-507,513-514,520,546-553 ----

@@ -204,6 +204,8 @@ int m1_allow_dynamic_lds(const void* kern, int bytes);
 // kernel-choice log (prof.hip; m1_debug_kernels in include/m1hip.h): the dispatch names the kernel behind every conv-like launch so
 // that a test of a special kernel can assert it ran (a declined shape would otherwise compare the generic kernel with itself)
 void m1_note_kernel(const char* fmt, ...);
+// plan log (prof.hip; m1_debug_plans): the splits, copies and fold behind a weight gradient, and the rungs that declined it
+void m1_note_plan(const char* fmt, ...);
 
 // profiler hooks (prof.hip)
 struct M1ProfScope {

@@ -628,6 +628,7 @@ static int wgrad_common(const m1_conv_desc_t* d, bool T, const void* dy, float* 
             int rc = f32 ? m1_t3s_wgrad(g, (long long)nw8, nbias, st) : m1_tf_wgrad(g, (long long)nw8, nbias, st);
             m1_fold_defer_set(was);
             if (rc == M1_OK) {
+                m1_note_plan("stem:cp=%d", CP);
                 hipLaunchKernelGGL(stem_fold_kernel, dim3((taps * Cin * d->Cout + 255) / 256), dim3(256), 0, st, r8, dw, taps, Cin, d->Cout, CP);
                 return m1_check_launch();
             }
@@ -650,6 +651,7 @@ static int wgrad_common(const m1_conv_desc_t* d, bool T, const void* dy, float* 
             if (wlog) fprintf(stderr, "wgrad %s N%d B %dx%dx%d CA %d x%d CB %d k%d%d%d s%d%d%d -> %s rc %d\n", T ? "convT" : "conv", g.N, g.BD,
                               g.BH, g.BW, g.CA, used, g.CB, g.kd, g.kh, g.kw, g.sd, g.sh, g.sw, took, rc);
             if (rc != M1_ERR_UNSUPPORTED && rc != M1_ERR_WORKSPACE) break;      // taken or a hard error; else declined: the next rung
+            m1_note_plan("decline:%s rc=%d", r.name, rc);
         }
         if (rc) return rc;
         for (int m = 0; m < used; ++m) off += d->src[i++].C;

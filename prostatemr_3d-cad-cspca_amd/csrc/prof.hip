@@ -79,6 +79,25 @@ extern "C" const char* m1_debug_kernels(int mode) {
     return out.c_str();
 }
 
+// ---- plan log: what the weight-gradient launchers, the fold and the ladder decided (splits, copies, fold kernel, declined rungs).  A log
+// of its own with the semantics of the kernel-choice log -- off until m1_debug_plans(1), up to 1 MB -- so that no assertion on kernel
+// names sees it; entries are separated by ';' (a grid is written "x,y,z").  Host side only, noted after a plan is final.
+namespace { bool g_plog_on = false; std::string g_plog; std::mutex g_plog_mu; }
+void m1_note_plan(const char* fmt, ...) {
+    if (!g_plog_on) return;
+    char buf[200];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+    std::lock_guard<std::mutex> lk(g_plog_mu);
+    if (g_plog.size() < (1u << 20)) { if (!g_plog.empty()) g_plog += ';'; g_plog += buf; }
+}
+extern "C" const char* m1_debug_plans(int mode) {
+    static std::string out;
+    std::lock_guard<std::mutex> lk(g_plog_mu);
+    out = g_plog;
+    if (mode >= 0) { g_plog.clear(); g_plog_on = mode != 0; }
+    return out.c_str();
+}
+
 // ---- debug: LDS canary.  Blocks fill 31 KB of static LDS (the footprint of thin_fwd_kernel) with a pattern and re-read it `spins`
 // times; *bad counts words that changed.  Run next to another kernel inside a graph (tools/dbg/stress_lds.py) it shows whether that
 // kernel writes LDS outside its own allocation (LDS-DMA is not bounds-checked against the workgroup's allocation).

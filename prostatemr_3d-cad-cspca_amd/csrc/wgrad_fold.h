@@ -18,7 +18,7 @@ struct WgCopyRule {
     long long max_bytes;     // ceiling on the bytes of all copies (0: none)
     WgShort on_short;
 };
-struct WgCopies { long long stride, rx_bias, nsplit; float* Rx; int rc; };
+struct WgCopies { long long stride, rx_bias, nsplit; float* Rx; int rc; long long fit; };     // fit: copies the region holds (plan log)
 // `want` splits of `ntiles` K-tiles under rule `r`; use_rx = false: the split count for a launch without copies
 static inline WgCopies m1_wg_copies(const WgradSpec& g, int taps, long long want, long long ntiles, const WgCopyRule& r, bool use_rx = true) {
     WgCopies c{};
@@ -30,6 +30,7 @@ static inline WgCopies m1_wg_copies(const WgradSpec& g, int taps, long long want
     if (r.max_copies && n > r.max_copies) n = r.max_copies;
     if (r.max_bytes && n * c.stride * 4 > r.max_bytes) n = r.max_bytes / (c.stride * 4);
     const long long fit = g.rx ? g.rx_floats / c.stride : 0;
+    c.fit = fit;
     if (r.on_short == WG_SHORT_ERROR) {
         if (fit < 1) { c.rc = M1_ERR_WORKSPACE; return c; }
         if (n > fit) n = fit;                                  // as many copies as the caller's scratch holds
@@ -61,6 +62,12 @@ static inline bool m1_wg_ktiles(const WgradSpec& g, int kt, int kws, long long m
     return nt < (1ll << 30) && nt >= min_tiles;
 }
 // both operands addressable with 32-bit voxel indices (tap, tf: DMA offsets relative to a tile origin, 2^20 voxels of slack)
+// the launcher's line of the plan log (m1_debug_plans), noted next to its m1_note_kernel once the plan is final
+static inline void m1_wg_note_plan(const char* name, long long tiles, long long want, long long splits, const WgCopies& c, bool rx, int stages,
+                                   unsigned gx, unsigned gy, unsigned gz) {
+    m1_note_plan("wg:%s tiles=%lld want=%lld splits=%lld fit=%lld rx=%d stages=%d grid=%u,%u,%u", name, tiles, want, splits, c.fit, (int)rx,
+                 stages, gx, gy, gz);
+}
 static inline bool m1_wg_vox32(const WgradSpec& g) {
     const long long lim = (1ll << 31) - (1 << 20);
     return (long long)g.N * g.AD * g.AH * g.AW < lim && (long long)g.N * g.BD * g.BH * g.BW < lim;

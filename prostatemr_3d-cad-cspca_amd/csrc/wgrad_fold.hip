@@ -159,6 +159,7 @@ static int launch_locked(hipStream_t st) {
             const TfPending& q = g_folds[i++];
             B.f[B.n] = q.f; B.mode[B.n] = q.mode; B.pref[B.n + 1] = B.pref[B.n] + q.blocks; ++B.n;
         }
+        m1_note_plan("foldbatch:n=%d blocks=%d", B.n, B.pref[B.n]);
         hipLaunchKernelGGL(tf_finish_batch_kernel, dim3((unsigned)B.pref[B.n]), dim3(256), 0, st, B);
         rc = m1_check_launch();
     }
@@ -205,6 +206,7 @@ int m1_wg_rx_finish(float* rx, long long stride, int ncopies, const WgradSpec& g
         while (f.EL > 4 && n / f.EL < 128) f.EL >>= 1;           // small blocks of R: more lane rows per element, more blocks
         blocks = (n + f.EL - 1) / f.EL;
     }
+    const char* const mname = mode == 1 ? "vec" : (mode == 2 ? "wide" : "generic");
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (g_defer) {
@@ -218,10 +220,12 @@ int m1_wg_rx_finish(float* rx, long long stride, int ncopies, const WgradSpec& g
                 if (q.f.R == f.R && q.f.a_off == f.a_off && q.f.b_off == f.b_off) { dup = true; break; }
             if (!dup) {
                 g_folds.push_back(TfPending{f, mode, (int)blocks});
+                m1_note_plan("fold:%s copies=%d n=%lld nb=%d el=%d queued", mname, ncopies, n, f.nb, f.EL);
                 return M1_OK;
             }
         }
     }
+    m1_note_plan("fold:%s copies=%d n=%lld nb=%d el=%d now", mname, ncopies, n, f.nb, f.EL);
     if (mode == 1) hipLaunchKernelGGL(tf_finish_vec_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f);
     else if (mode == 2) hipLaunchKernelGGL(tf_finish_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f);
     else hipLaunchKernelGGL(tf_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f);

@@ -258,6 +258,7 @@ static int launch_wg(WgP p, hipStream_t st) {
     // scratch holds fewer copies; one split needs none (a single add per element and launch is ordered by the stream).
     int det = M1_CFG("M1_WG_DET", 1);
     const bool small = (long long)taps * p.CA * p.CB <= 32768 && splits >= 24;
+    const long long want = splits;
     const WgCopies c = m1_wg_copies(p, taps, splits, 0, WG_COPIES, det || small);
     p.rx_stride = c.stride; p.rx_bias = c.rx_bias; p.Rx = nullptr;
     if (c.Rx) {
@@ -270,9 +271,11 @@ static int launch_wg(WgP p, hipStream_t st) {
     if (xr && (long long)grid.x * grid.y > 1 && splits > 1) {
         p.xcd_total = (int)(((long long)grid.x * grid.y * grid.z + 7) / 8 * 8);
         m1_note_kernel("wgrad_mfma");
+        m1_wg_note_plan("wgrad_mfma", TV, want, splits, c, partial, 0, (unsigned)p.xcd_total, 1, 1);
         hipLaunchKernelGGL((wgrad_mfma_kernel<T, TA, TB, KB>), dim3((unsigned)p.xcd_total), dim3(256), 0, st, p);
     } else {
         m1_note_kernel("wgrad_mfma");
+        m1_wg_note_plan("wgrad_mfma", TV, want, splits, c, partial, 0, grid.x, grid.y, grid.z);
         hipLaunchKernelGGL((wgrad_mfma_kernel<T, TA, TB, KB>), grid, dim3(256), 0, st, p);
     }
     int rc = m1_check_launch(); if (rc) return rc;

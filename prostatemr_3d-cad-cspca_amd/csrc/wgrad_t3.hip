@@ -575,7 +575,8 @@ int m1_t3_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st, int nm
     const int gx = bigb ? g.CB / 128 : g.CB / 64, gzu = bigb ? p.nunits : (p.nunits + 1) / 2;
     const long long per_split = (long long)gx * gzu * g.kd;    // blocks per voxel split
     int tgt = M1_CFG("M1_T3_BLOCKS", 256);      // one block per CU
-    const WgCopies c = m1_wg_copies(g, g.kd * 9, tgt / per_split, p.ntiles, T3_COPIES);
+    const long long want = tgt / per_split;
+    const WgCopies c = m1_wg_copies(g, g.kd * 9, want, p.ntiles, T3_COPIES);
     if (c.rc) return c.rc;
     const long long nsplit = c.nsplit, stride = c.stride, nloc = c.rx_bias;
     // too small to fill the chip at that depth (single layers of the (10,20,20) level): the per-tap kernel, with 27 x more
@@ -604,7 +605,10 @@ int m1_t3_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st, int nm
     else if (bigb) kern = p.KWs == 8 ? wgrad_t3_kernel<8, true, 1> : (p.KWs == 16 ? wgrad_t3_kernel<16, true, 1> : (p.KWs == 32 ? wgrad_t3_kernel<32, true, 1> : wgrad_t3_kernel<0, true, 1>));
     else kern = p.KWs == 8 ? wgrad_t3_kernel<8, false, 1> : (p.KWs == 16 ? wgrad_t3_kernel<16, false, 1> : (p.KWs == 32 ? wgrad_t3_kernel<32, false, 1> : wgrad_t3_kernel<0, false, 1>));
     if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
-    m1_note_kernel(f32 ? "wgrad_t3f:kws%d:big%d" : (s2 ? "wgrad_t3:s2:kws%d:big%d" : "wgrad_t3:kws%d:big%d"), p.KWs, (int)bigb);
+    char name[48];                                             // (one name for both logs)
+    snprintf(name, sizeof(name), f32 ? "wgrad_t3f:kws%d:big%d" : (s2 ? "wgrad_t3:s2:kws%d:big%d" : "wgrad_t3:kws%d:big%d"), p.KWs, (int)bigb);
+    m1_note_kernel("%s", name);
+    m1_wg_note_plan(name, p.ntiles, want, nsplit, c, true, S, (unsigned)gx, (unsigned)nsplit, (unsigned)(gzu * g.kd));
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)nsplit, (unsigned)(gzu * g.kd)), dim3(T3_THREADS), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;
     return m1_wg_fold_members(p.Rx, p.rx_mem, stride, (int)nsplit, g, nloc, nmem, a_offs, st);

@@ -257,7 +257,8 @@ int m1_t3s_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     const int nbu = (g.CB + TLh - 1) / TLh;
     const long long per_split = (long long)nbu * p.nau * g.kd;
     int tgt = M1_CFG("M1_T3S_BLOCKS", 256);
-    const WgCopies c = m1_wg_copies(g, g.kd * 9, tgt / per_split, p.ntiles, TS_COPIES);
+    const long long want = tgt / per_split;
+    const WgCopies c = m1_wg_copies(g, g.kd * 9, want, p.ntiles, TS_COPIES);
     if (c.rc) return c.rc;
     const long long nsplit = c.nsplit, stride = c.stride, nloc = c.rx_bias;
     p.nsplit = (int)nsplit;
@@ -282,6 +283,7 @@ int m1_t3s_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
 #undef TSK
     if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_t3s");
+    m1_wg_note_plan("wgrad_t3s", p.ntiles, want, nsplit, c, true, S, (unsigned)nbu, (unsigned)nsplit, (unsigned)(p.nau * g.kd));
     hipLaunchKernelGGL(kern, dim3((unsigned)nbu, (unsigned)nsplit, (unsigned)(p.nau * g.kd)), dim3(TS_THREADS), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;
     return m1_wg_rx_finish(p.Rx, stride, (int)nsplit, g, nloc, st);
@@ -426,13 +428,15 @@ int m1_pwf_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     p.ntiles = (int)((p.V + PW_KT - 1) / PW_KT);
     const int nau = (g.CA + 63) / 64, nbu = (g.CB + 63) / 64;
     int tgt = M1_CFG("M1_PWF_BLOCKS", 256);     // one block per CU (128 KB of LDS)
-    const WgCopies c = m1_wg_copies(g, 1, tgt / (nau * nbu), p.ntiles, PW_COPIES);
+    const long long want = tgt / (nau * nbu);
+    const WgCopies c = m1_wg_copies(g, 1, want, p.ntiles, PW_COPIES);
     if (c.rc) return c.rc;
     const long long nsplit = c.nsplit, stride = c.stride, nloc = c.rx_bias;
     p.nsplit = (int)nsplit; p.Rx = c.Rx; p.rx_stride = stride; p.rx_bias = nloc; p.want_bsum = g.bsum != nullptr;
     const size_t smem = 2 * (size_t)(2 * (PW_KT / 4) * 1024);
     if (m1_allow_dynamic_lds((const void*)wgrad_pwf_kernel, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_pwf");
+    m1_wg_note_plan("wgrad_pwf", p.ntiles, want, nsplit, c, true, 0, (unsigned)nbu, (unsigned)nsplit, (unsigned)nau);
     hipLaunchKernelGGL(wgrad_pwf_kernel, dim3((unsigned)nbu, (unsigned)nsplit, (unsigned)nau), dim3(PW_THREADS), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;
     return m1_wg_rx_finish(p.Rx, stride, (int)nsplit, g, nloc, st);

@@ -275,9 +275,11 @@ int m1_tap_wgrad(const WgradSpec& g, long long nw, int nb, hipStream_t st) {
     if (xr && taps > 1) {
         p.xcd_total = (int)(((long long)ctiles * nsplit * taps + 7) / 8 * 8);
         m1_note_kernel("wgrad_tap");
+        m1_wg_note_plan("wgrad_tap", p.ntiles, want, nsplit, c, p.Rx != nullptr, S, (unsigned)p.xcd_total, 1, 1);
         hipLaunchKernelGGL(kern, dim3((unsigned)p.xcd_total), dim3(256), smem, st, p);
     } else {
         m1_note_kernel("wgrad_tap");
+        m1_wg_note_plan("wgrad_tap", p.ntiles, want, nsplit, c, p.Rx != nullptr, S, (unsigned)ctiles, (unsigned)nsplit, (unsigned)taps);
         hipLaunchKernelGGL(kern, dim3(ctiles, (unsigned)nsplit, taps), dim3(256), smem, st, p);
     }
     int rc = m1_check_launch(); if (rc) return rc;

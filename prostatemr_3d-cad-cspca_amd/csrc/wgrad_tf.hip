@@ -308,7 +308,8 @@ static int tf_wgrad_launch(const WgradSpec& g, long long nw, int nb, hipStream_t
     // kernels fill the idle SIMDs: C3 (4 volumes per launch) -2 % with 512, C2 (2 volumes) +1 %
     int tgt_env = M1_CFG("M1_TF_SPLIT", 0);
     const int tgt = tgt_env > 0 ? tgt_env : (p.ntiles >= 24576 ? 512 : 256);
-    const WgCopies c = m1_wg_copies(g, g.kd * g.kh * g.kw, (tgt + ctiles - 1) / ctiles, p.ntiles, TF_COPIES);      // (rounded UP)
+    const long long want = (tgt + ctiles - 1) / ctiles;                                                        // (rounded UP)
+    const WgCopies c = m1_wg_copies(g, g.kd * g.kh * g.kw, want, p.ntiles, TF_COPIES);
     if (c.rc) return c.rc;
     const long long nsplit = c.nsplit;
     p.nsplit = (int)nsplit;
@@ -332,6 +333,7 @@ static int tf_wgrad_launch(const WgradSpec& g, long long nw, int nb, hipStream_t
     if (!kern) return M1_ERR_UNSUPPORTED;
     if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_tf");
+    m1_wg_note_plan("wgrad_tf", p.ntiles, want, nsplit, c, true, p.stages, grid.x, grid.y, grid.z);
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p);
     int rc = m1_check_launch(); if (rc) return rc;
     return m1_wg_fold_members(p.Rx, rx_mem, c.stride, (int)nsplit, g, c.rx_bias, nmem < 1 ? 1 : nmem, a_offs, st);

@@ -1956,6 +1956,25 @@ class kernel_log:
         return any(n == prefix or n.startswith(prefix + ":") for n in self.names)
 
 
+class plan_log:
+    """``with ops.plan_log() as pl: ...; pl.entries`` -- what the weight-gradient launchers, the fold and the ladder decided inside the
+    block (m1_debug_plans), e.g. ['wg:wgrad_tf tiles=150 want=64 splits=64 fit=512 rx=1 stages=8 grid=4,64,1',
+    'fold:generic copies=64 n=9248 nb=32 el=32 queued', 'foldbatch:n=1 blocks=289'].  ``pl.of('fold:')``: the entries with that prefix."""
+
+    def __enter__(self):
+        L.load().m1_debug_plans(1)
+        self.entries = []
+        return self
+
+    def __exit__(self, *exc):
+        raw = L.load().m1_debug_plans(0)
+        self.entries = [n for n in (raw.decode() if raw else "").split(";") if n]
+        return False
+
+    def of(self, prefix: str):
+        return [n for n in self.entries if n.startswith(prefix)]
+
+
 def prof_enable(on: bool):
     L.load().m1_prof_enable(1 if on else 0)
 

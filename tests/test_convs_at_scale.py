@@ -731,9 +731,10 @@ def test_same_parameter_twice_in_the_queue(dev, q, monkeypatch):
     passes of a step).  Two read-modify-writes of the same block must not share a batched launch:
     * fold: the second fold into a queued (R, a_off, b_off) runs at once on its call's stream, the queued one stays (m1_wg_rx_finish);
     * column sum (transposed conv, db): a second sum into a queued ``out`` is declined and the caller reduces in place (m1_colsum_defer).
-    The kernel log has no entry for folds or column sums, so what was queued is read off the sinks between the calls: with the weight
-    gradients launched in place, a queued fold / sum leaves its sink untouched, one that ran at once has added one gradient; after
-    fold_pending both hold two.  The same through the deferred launches (both calls inside one m1_wgrad_defer window), twice: equal
+    The plan log (ops.plan_log) says of every fold whether it was queued or ran at once: with the weight gradients launched in place
+    the first call's folds are all "queued", the second call's all "now", and fold_pending launches one batch that holds the first call's.
+    The column sums have no log entry, so for them (and once more for the folds) what was queued is read off the sinks between the
+    calls: a queued fold / sum leaves its sink untouched, one that ran at once has added one gradient; after fold_pending both hold two.  The same through the deferred launches (both calls inside one m1_wgrad_defer window), twice: equal
     bits run to run.  Not compared bit for bit ACROSS the two orders: which call folds first may change the last bit."""
     key = _key(*q)
     name, N, D, H, W, cins, cout, k, s, dts, fl, kern = key
@@ -747,11 +748,17 @@ def test_same_parameter_twice_in_the_queue(dev, q, monkeypatch):
     def run(in_place):
         wd, bd = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
         wd._m1_gsink, bd._m1_gsink = pre_w.clone(), pre_b.clone()
+        folds = []                                            # per backward pass: its "fold:" entries of the plan log
         with ops.config(M1_T3_MIN_BLOCKS=128), ops.kernel_log() as kl:
             for i in range(2):
                 y = (ops.conv3d_transpose_same if tr else ops.conv3d_same)([x.to(dtype) for x in xs], wd, bd, k, s)
-                y.backward(dy.to(dtype))
+                with ops.plan_log() as pl:
+                    y.backward(dy.to(dtype))
+                folds.append(pl.of("fold:"))
                 if in_place:
+                    # the first call's folds are queued; the second finds its (R, a_off, b_off) in the queue and folds at once
+                    assert folds[i] and all(f.endswith(" now" if i else " queued") for f in folds[i]), (i, folds[i])
+                    assert not pl.of("foldbatch:"), pl.entries
                     torch.cuda.synchronize()
                     if i == 0:                                # queued: nothing has touched the sinks
                         assert torch.equal(wd._m1_gsink, pre_w) and torch.equal(bd._m1_gsink, pre_b), key
@@ -759,8 +766,17 @@ def test_same_parameter_twice_in_the_queue(dev, q, monkeypatch):
                         once["w"], once["b"] = wd._m1_gsink.clone(), bd._m1_gsink.clone()
             if not in_place:
                 assert len(ops._WGP["jobs"]) == 2 and not [n for n in kl.names if n.startswith("wgrad")], (len(ops._WGP["jobs"]), kl.names)
-            ops.fold_pending()
-            torch.cuda.synchronize()
+                assert folds == [[], []], folds               # (nothing launched, nothing folded or queued yet)
+            with ops.plan_log() as pl:
+                ops.fold_pending()
+                torch.cuda.synchronize()
+            late, batch = pl.of("fold:"), pl.of("foldbatch:")
+            if in_place:                                      # one batch: exactly the folds the first call queued
+                assert not late and batch == [f"foldbatch:n={len(folds[0])} blocks={batch[0].split('blocks=')[1]}"], (late, batch)
+            else:                                             # both calls launched here, in order: the first queues, the second folds at once
+                assert len(late) % 2 == 0 and late[:len(late) // 2] == [f.replace(" now", " queued") for f in late[len(late) // 2:]], late
+                assert all(f.endswith(" queued") for f in late[:len(late) // 2]) and len(batch) == 1, (late, batch)
+                assert batch[0].startswith(f"foldbatch:n={len(late) // 2} "), (late, batch)
         assert not ops._WGP["jobs"] and not ops._FOLD["keep"]
         assert [n for n in kl.names if n.startswith("wgrad")] == 2 * kern.split("+"), kl.names      # (partial-copy kernels, both times)
         return wd._m1_gsink, bd._m1_gsink
