@@ -2,6 +2,7 @@
 // inline asm with their waits, counted vmcnt waits, the 64-byte-row swizzle, the bf16 pack.  A helper that one file uses stays there.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -51,6 +52,11 @@ __device__ __forceinline__ u32x2_t m1_tr_read_asm(unsigned lds_addr) {
 // all outstanding LDS reads have landed; tying the fragment makes its consumers wait behind this statement
 __device__ __forceinline__ void m1_lds_wait(u32x4_t& v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)); }
 __device__ __forceinline__ void m1_lds_wait(u32x2_t& a, u32x2_t& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)); }
+// the same with at most N younger LDS reads still in flight (LDS reads return in order)
+template <int N> __device__ __forceinline__ void m1_lds_wait_n(u32x2_t& a, u32x2_t& b) {
+    static_assert(N >= 0 && N <= 15, "lgkmcnt immediate");
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
+}
 // no instruction: only orders the consumers of v behind the preceding (volatile) wait
 __device__ __forceinline__ void m1_lds_tie(u32x4_t& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ bf16x8_t m1_frag8(u32x2_t lo, u32x2_t hi) {
@@ -83,4 +89,9 @@ __device__ __forceinline__ int m1_swz64(int row, int seg) { return seg ^ ((-(row
 // pack two floats to bf16x2 (round to nearest even): one v_cvt_pk_bf16_f32
 __device__ __forceinline__ unsigned m1_cvt_pk_bf16(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
+}
+
+// f(integral_constant<int, I>) for I = B .. E - 1: an unrolled loop whose index is a constant expression (asm immediates, slot numbers)
+template <int B, int E, class F> __device__ __forceinline__ void m1_static_for(F&& f) {
+    if constexpr (B < E) { f(std::integral_constant<int, B>{}); m1_static_for<B + 1, E>(f); }
 }

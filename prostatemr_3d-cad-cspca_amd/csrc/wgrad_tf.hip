@@ -12,7 +12,8 @@
 //   different ROW offset into the same A tile (no register transposes, no unaligned LDS reads).
 //   Probe of the instruction's lane mapping: tools/probes/tr_b16_probe.hip.
 // * wave w accumulates the 16x16 tile (w>>1, w&1) of every tap: NT x 4 accumulator registers; the B fragment of a
-//   k-step is read once and reused by all taps.
+//   k-step is read once and reused by all taps.  With 32 channels on both sides (KPARTS == 1) the M32 body runs instead: one
+//   wave per 32x32 tile of its own taps on v_mfma_f32_32x32x16_bf16 (see there).
 // * K-tiles are dealt round-robin to the blocks of a channel tile; every block stores its partial tile into its own copy of the
 //   member's gradient block and a fold (wgrad_fold.hip: tf_finish_*, queued and run in batches) adds the copies in a fixed
 //   order -- no floating-point atomics.  The equal-width members of a concat share one launch (blockIdx.z = member).
@@ -47,8 +48,10 @@ struct TfP {
 
 #define TF_MAX_STAGES 8
 
-template <int KD, int KH, int KW, int KPARTS, int TF_NKS>
-__global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
+// M32 (KPARTS == 1 only, M1_TF_MFMA32): the 32x32x16 body -- one wave computes the whole 32 x 32 tile of ITS taps (see below);
+// staging, K-tiles, pipeline and the partial-copy layout are the same code.
+template <int KD, int KH, int KW, int KPARTS, int TF_NKS, bool M32 = false>
+__global__ void __launch_bounds__(256, M32 ? 2 : 1) wgrad_tf_kernel(TfP p) {
 #if defined(__HIP_DEVICE_COMPILE__)      // (buffer-resource builtins do not exist in the host pass)
     constexpr int NT = KD * KH * KW, NG = KD * KH;           // taps; tap groups (the KW taps of one (kd,kh) share a row offset)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -146,6 +149,128 @@ __global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
                                                          (b_inner || bh0 + b_th[it] < p.BH) ? b_vo[it] : OOB, 0, 0, 0);
     };
 
+    if constexpr (M32) {
+    // ---- v_mfma_f32_32x32x16_bf16, waves split by TAP (both sides 32 channels: 64-byte rows).  Wave w owns the taps t = w + 4 j
+    //      (9 taps: 3/2/2/2, 27: 7/7/7/6) and accumulates their whole 32 x 32 tile: the dY fragment of a 16-voxel k-step is read once
+    //      per wave, an X fragment by exactly one wave -- 52 / 124 transpose reads per 32 voxels and block where the 16x16x32 body
+    //      below issues 80 / 224.  Operand layout as in wgrad_t3.hip: lane l supplies channel l & 31, k = 8 (l >> 5) ..; lane
+    //      (g2 = l >> 4, i = l & 15) points at voxel 16 ks + 8 (g2 >> 1) + 4 h + (i >> 2), 16-channel half g2 & 1, 8-byte piece
+    //      i & 3.  Lanes 0-31 (one LDS cycle) read both halves of 4 rows: with stride 1 four consecutive 64-byte rows = all 64
+    //      banks once, whatever the half swap of the staging does (both halves of a row are read) -- the DMA side stays as it is.
+    const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
+    const int S = p.stages;
+    const int npiece = nait + nbit;                            // LDS-DMA pieces per wave per stage
+    const long long kt0 = blockIdx.y, step = p.nsplit;
+    static_assert(KPARTS == 1 && KW == 3, "the tap split assumes 32 x 32 tiles and t % KW == (w + j) % KW");
+    constexpr int NK = 2 * TF_NKS, NTW = (NT + 3) / 4;         // k-steps of 16 voxels per K-tile; taps per wave (the last may be missing)
+    const int g2 = lane >> 4, i = lane & 15, kg = g2 >> 1, ch = g2 & 1;
+    // byte addresses inside stage 0 of k-step 0, tap row (kd,kh) = (0,0); a_ad[h][r]: kw = (wave + r) % KW.  K-step ks lies 16 ks voxel
+    // slots on: whole rows and multiples of 16 columns (KWs = 8 / 16 / 32), which leave the half swap (bit 3 of the column) alone --
+    // a wave-uniform offset, (ks >> 1) * ko2 + (ks & 1) * ko1 for X and 16 ks rows for dY
+    unsigned a_ad[2][KW], b_ad[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int kk = 8 * kg + 4 * h + (i >> 2);
+        const int th = kk / p.KWs, tw = kk - th * p.KWs;
+#pragma unroll
+        for (int r = 0; r < KW; ++r) {
+            const int ww = tw * p.sw + (wave + r) % KW;
+            a_ad[h][r] = lds0 + ((th * p.sh) * p.AWt + ww) * PA + (ch ^ ((ww >> 3) & 1)) * 32 + (i & 3) * 8;
+        }
+        b_ad[h] = lds0 + p.a_bytes + kk * PB + (ch ^ ((tw >> 3) & 1)) * 32 + (i & 3) * 8;
+    }
+    const unsigned ko1 = (unsigned)(((16 / p.KWs) * p.sh * p.AWt + (16 % p.KWs) * p.sw) * PA);
+    const unsigned ko2 = (unsigned)(((32 / p.KWs) * p.sh * p.AWt + (32 % p.KWs) * p.sw) * PA);
+    unsigned ro[NTW];                                          // (wave-uniform) byte offset of the tap row (kd,kh) of tap j
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {
+        const int tg = (wave + 4 * j) / KW;
+        ro[j] = (unsigned)(((tg / KH) * p.AHt + tg % KH) * p.AWt * PA);
+    }
+    const bool last_ok = wave + 4 * (NTW - 1) < NT;            // this wave has NTW taps (else NTW - 1)
+
+    f32x16_t acc[NTW];
+#pragma unroll
+    for (int j = 0; j < NTW; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    const bool do_bsum = p.bsum != nullptr && a0 == 0 && wave == 3 && mem == 0;      // (wave 3 has the fewest taps)
+    // bias sums as the 16x16x32 body takes them, a ones operand in front of the dY fragment (every row of the tile = the column sums): the
+    // MFMA adds its k values in order, so two K = 16 steps leave the bits one K = 32 step leaves -- the same holds for the taps
+    f32x16_t accb;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) accb[e] = 0.f;
+    const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u));
+
+    // the K-tile at stage offset sb for a wave with N taps, as a flat list of ITEMS of two transpose reads each: per k-step the dY
+    // fragment, then the X fragments of the N taps (one MFMA each).  Reads run D items ahead of the MFMAs through a ring of D + 1
+    // fragment slots; LDS reads return in order, so item m has landed once at most 2 * (items issued after m) reads are in flight.
+    auto tile = [&](unsigned sb, auto n_c) {
+        constexpr int N = decltype(n_c)::value, NI = NK * (N + 1);
+        constexpr int D = N + 1 < 6 ? N + 1 : 6, RS = D + 1;   // (D <= N + 1: the dY fragment of k-step u lives until u + 2 is read)
+        u32x2_t bl[2], bh[2], al[RS], ah[RS];
+        auto rd = [&](auto m_c) {
+            constexpr int m = decltype(m_c)::value, u = m / (N + 1), j = m % (N + 1) - 1;
+            if constexpr (j < 0) {
+                const unsigned so = sb + (unsigned)(u * 16) * PB;
+                bl[u & 1] = m1_tr_read_asm(b_ad[0] + so); bh[u & 1] = m1_tr_read_asm(b_ad[1] + so);
+            } else {
+                constexpr int sl = (u * N + j) % RS;
+                const unsigned so = sb + ro[j] + (u >> 1) * ko2 + (u & 1) * ko1;
+                al[sl] = m1_tr_read_asm(a_ad[0][j % KW] + so); ah[sl] = m1_tr_read_asm(a_ad[1][j % KW] + so);
+            }
+        };
+        m1_static_for<0, D>(rd);
+        bf16x8_t bfr;
+        m1_static_for<0, NI>([&](auto m_c) {
+            constexpr int m = decltype(m_c)::value, u = m / (N + 1), j = m % (N + 1) - 1;
+            if constexpr (m + D < NI) rd(std::integral_constant<int, m + D>{});
+            constexpr int after = NI - 1 - m < D ? NI - 1 - m : D;
+            if constexpr (j < 0) {
+                m1_lds_wait_n<2 * after>(bl[u & 1], bh[u & 1]);
+                bfr = m1_frag8(bl[u & 1], bh[u & 1]);
+                if (do_bsum) accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, bfr, accb, 0, 0, 0);
+            } else {
+                constexpr int sl = (u * N + j) % RS;
+                m1_lds_wait_n<2 * after>(al[sl], ah[sl]);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(m1_frag8(al[sl], ah[sl]), bfr, acc[j], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    };
+
+    // the S-deep pipeline of the 16x16x32 body below around `tile(stage byte offset)`
+    auto run_tiles = [&](auto&& tile_fn) {
+        for (int s = 0; s < S - 1; ++s) issue(s);
+        int st = 0;
+        for (long long kt = kt0; kt < p.ntiles; kt += step) {
+            m1_wait_vm<48>(npiece * (S - 2));         // this wave's pieces of tile kt have landed ...
+            __builtin_amdgcn_s_barrier();                      // ... and everybody's; everybody is also done with tile kt - step
+            int stn = st + S - 1; if (stn >= S) stn -= S;
+            issue(stn);                                        // refill the buffer tile kt - step was read from
+            tile_fn((unsigned)(st * stage_bytes));
+            if (++st == S) st = 0;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the padding stages of the tail
+    };
+    // (one K loop per tap count: a choice inside the loop makes the accumulators change registers where the two paths meet)
+    if (last_ok) run_tiles([&](unsigned sb) { tile(sb, std::integral_constant<int, NTW>{}); });
+    else run_tiles([&](unsigned sb) { tile(sb, std::integral_constant<int, NTW - 1>{}); });
+
+    // ---- D[a][b] of a 32x32 tile: lane holds b = lane & 31, a = (e & 3) + 8 (e >> 2) + 4 (lane >> 5); same copy layout as below ----
+    float* Rx = p.Rx + (long long)mem * p.rx_mem + (long long)blockIdx.y * p.rx_stride;
+    const int b = b0 + (lane & 31);
+    if (do_bsum && lane < 32 && b < p.CB) Rx[p.rx_bias + b] = accb[0];
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {
+        const int t = wave + 4 * j;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int a = a0 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+            if (t < NT && a < p.CA && b < p.CB) Rx[((long long)t * p.CA + a) * p.CB + b] = acc[j][e];
+        }
+    }
+    } else {
     // ---- fragment read addresses: lane (g = lane>>4, i = lane&15) supplies voxel 8g + 4h + (i>>2), 8-byte piece i&3 ----
     const int g = lane >> 4, i = lane & 15;
     const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
@@ -239,6 +364,7 @@ __global__ void __launch_bounds__(256) wgrad_tf_kernel(TfP p) {
             const int a = a0 + ta * 16 + g * 4 + r;
             if ((t % kparts) == part && a < p.CA && b < p.CB) Rx[((long long)t * p.CA + a) * p.CB + b] = acc[t][r];
         }
+    }
 #endif
 }
 
@@ -330,6 +456,12 @@ static int tf_wgrad_launch(const WgradSpec& g, long long nw, int nb, hipStream_t
     if (p.nks == 4 && kparts == 4) kern = g.kd == 1 ? wgrad_tf_kernel<1, 3, 3, 4, 4> : (g.kd == 3 ? wgrad_tf_kernel<3, 3, 3, 4, 4> : nullptr);
     if (p.nks == 4 && g.kd == 1 && kparts == 1) kern = wgrad_tf_kernel<1, 3, 3, 1, 4>;
     if (p.nks == 4 && g.kd == 1 && kparts == 2) kern = wgrad_tf_kernel<1, 3, 3, 2, 4>;
+    // 32 channels on both sides: the 32x32x16 body with the waves split by tap (same plan, grid, stages and copies).  M1_TF_MFMA32: 0 = the
+    // 16x16x32 body everywhere
+    if (kparts == 1 && kern && M1_CFG("M1_TF_MFMA32", 1)) {
+        if (g.kd == 3) kern = wgrad_tf_kernel<3, 3, 3, 1, 2, true>;
+        else kern = p.nks == 4 ? wgrad_tf_kernel<1, 3, 3, 1, 4, true> : wgrad_tf_kernel<1, 3, 3, 1, 2, true>;
+    }
     if (!kern) return M1_ERR_UNSUPPORTED;
     if (m1_allow_dynamic_lds((const void*)kern, 160 * 1024) != M1_OK) return M1_ERR_LAUNCH;
     m1_note_kernel("wgrad_tf");
