@@ -373,6 +373,32 @@ int m1_mc_accum_v(const void* logits, int R, int B, int D, int H, int W, int nc,
                   float* sum_h, float* sum_pp, int accumulate, float* samples_out, void* stream);
 int m1_tta_views(const void* x, int B, int D, int H, int W, int C, int dtype, int R, unsigned long long flips, void* out, void* stream);
 
+/* ---- Sliding-window inference (csrc/tile.hip; unets.networks.predict_tiled is the public surface, tiling.py the host side) ----
+ * A volume (B, vol[0], vol[1], vol[2], C) larger than the network's grid is cut into T = n[0] * n[1] * n[2] overlapping tiles of the
+ * network's size, tile t = (i0 * n[1] + i1) * n[2] + i2 at (origin[0][i0], origin[1][i1], origin[2][i2]).  The geometry travels by
+ * value into the kernels: no device table, no memcpy node, so the calls can be captured.  Per axis a: origin[a][0 .. n[a]) strictly
+ * ascending, 0 <= origin and origin + tile[a] <= vol[a] (a tile never leaves the volume: there is no padding here), and the tiles
+ * together cover [0, vol[a]): origin[a][0] == 0, no gap between neighbours, the last tile ends at vol[a].
+ * m1_tile_gather: x (B, vol..., C) fp32 / bf16, any C >= 1 -> out (T*B, tile..., C) of the same type, tile-major: sample t * B + b is
+ * tile t of batch entry b.  A copy, one launch.  16-byte accesses when both pointers are 16-byte aligned and vol[2], tile[2] and
+ * every origin[2][] are multiples of m = 16 / gcd(16, C * element size) voxels; element accesses otherwise, same bits.
+ * m1_tile_blend: tiles (T*B, tile..., C) fp32 in that order (the MC accumulators, or any per-voxel map; C = 1 for sum_h), profile =
+ * the device rows w0[tile[0]], w1[tile[1]], w2[tile[2]] one after the other, fp32, all > 0 (the caller's promise: the kernel cannot
+ * refuse them before it runs) -> out (B, vol..., C) fp32.  One lane owns output voxels and reads every tile that covers them: no
+ * atomics, no workspace, no zero fill, no memset node; one launch; bit-identical from run to run and for every grid.  Per voxel, the
+ * covering tiles i in ascending t: w_i = (w0 * w1) * w2 at the voxel's position inside tile i, W = sum_i w_i, out_c = sum_i
+ * (w_i / W) * v_i,c, each sum in that order starting from its first term, every operation a separate fp32 rounding, IEEE division.
+ * A voxel that one tile covers receives that tile's value bit for bit.  16-byte accesses when C <= 4, both tensors are 16-byte
+ * aligned and vol[2], tile[2] and every origin[2][] are multiples of G = 4, 2, 4, 1 voxels for C = 1, 2, 3, 4; element accesses
+ * otherwise, same bits.
+ * NULL pointers, B, C or an extent < 1, n[a] outside 1..M1_TILE_MAX_AXIS, origins that break the rules above, a pointer not aligned
+ * to its element: M1_ERR_BAD_ARG.  A dtype outside the enum, T * B * tile voxels * C or B * vol voxels * C >= 2^31:
+ * M1_ERR_UNSUPPORTED.  Both before any launch. */
+#define M1_TILE_MAX_AXIS 16
+typedef struct { int vol[3]; int tile[3]; int n[3]; int origin[3][M1_TILE_MAX_AXIS]; } m1_tile_t;
+int m1_tile_gather(const void* x, int B, int C, int dtype, const m1_tile_t* g, void* out, void* stream);
+int m1_tile_blend(const float* tiles, int B, int C, const m1_tile_t* g, const float* profile, float* out, void* stream);
+
 /* ---- Focal loss on the softmax heads : losses.py:32-49 (FL: renormalise, clip [1e-7, 1-1e-7], -y log p, * y (1-p)^gamma,
  * * alpha, sum over D,H,W,C, mean over the batch; loss(): mean over the y_pred.shape[-1] / nc heads) ----
  * probs (N,V,nheads*nc) fp32 as written by m1_softmax_heads_fwd; y_true (N,V,nc) fp32 or bf16; alpha: nc HOST floats.

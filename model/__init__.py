@@ -1,5 +1,5 @@
 """Reference-shaped import path: ``import model.unets as unets; import model.losses as losses`` (as in the
-reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators``, ``model.preprocess``, ``model.detection``, ``model.surface_distance``, ``model.calibration``, ``model.bootstrap`` and ``model.validation`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
+reference's train_model.py:19-22, ``model.augmentations``, ``model.data_generators``, ``model.preprocess``, ``model.detection``, ``model.surface_distance``, ``model.calibration``, ``model.bootstrap``, ``model.validation`` and ``model.tiling`` included) resolves to the MI355X-native package ``prostatemr_3d-cad-cspca_amd``."""
 import importlib
 import os
 import sys
@@ -20,6 +20,7 @@ surface_distance = _pkg.surface_distance
 calibration = _pkg.calibration
 bootstrap = _pkg.bootstrap
 validation = _pkg.validation
+tiling = _pkg.tiling
 sys.modules[__name__ + ".unets"] = unets
 sys.modules[__name__ + ".unets.networks"] = unets.networks
 sys.modules[__name__ + ".unets.network_blocks"] = unets.network_blocks
@@ -33,3 +34,4 @@ sys.modules[__name__ + ".surface_distance"] = surface_distance
 sys.modules[__name__ + ".calibration"] = calibration
 sys.modules[__name__ + ".bootstrap"] = bootstrap
 sys.modules[__name__ + ".validation"] = validation
+sys.modules[__name__ + ".tiling"] = tiling

@@ -23,6 +23,7 @@ from . import surface_distance  # noqa: F401
 from . import calibration    # noqa: F401
 from . import bootstrap      # noqa: F401
 from . import validation     # noqa: F401
+from . import tiling         # noqa: F401
 
 __all__ = ["hip", "initializers", "losses", "optim", "unets", "ddp", "augmentations", "data_generators", "preprocess", "detection",
-           "surface_distance", "calibration", "bootstrap", "validation"]
+           "surface_distance", "calibration", "bootstrap", "validation", "tiling"]

@@ -93,6 +93,15 @@ class m1_restore_t(C.Structure):
 
 M1_RESTORE_MAX_SEL = 4              # the widest channel selection m1_restore stores with vector stores (wider: element stores)
 
+M1_TILE_MAX_AXIS = 16
+
+
+class m1_tile_t(C.Structure):
+    """The tile geometry of m1_tile_gather / m1_tile_blend (include/m1hip.h): per axis the volume's and the tile's length, the number
+    of tiles and their ascending origins (``tiling.tile_geometry`` fills it)."""
+    _fields_ = [("vol", C.c_int * 3), ("tile", C.c_int * 3), ("n", C.c_int * 3), ("origin", (C.c_int * M1_TILE_MAX_AXIS) * 3)]
+
+
 class m1_cc_row_t(C.Structure):
     """One component's row of m1_cc_stats (include/m1hip.h); ``CC_ROW_DTYPE`` in hip/ops.py is the same layout for numpy."""
     _fields_ = [("count", C.c_int32), ("vmax", C.c_float), ("argmax", C.c_int64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
@@ -213,6 +222,8 @@ SIGNATURES = {
     "m1_mc_finish_u": (_i, [_vp, _vp, _vp, _i, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "m1_mc_accum_v": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _u64, _vp, _vp, _vp, _i, _vp, _vp]),
     "m1_tta_views": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _u64, _vp, _vp]),
+    "m1_tile_gather": (_i, [_vp, _i, _i, _i, C.POINTER(m1_tile_t), _vp, _vp]),
+    "m1_tile_blend": (_i, [_vp, _i, _i, C.POINTER(m1_tile_t), _vp, _vp, _vp]),
     "m1_focal_ws_floats": (_sz, [_i, _ll, _i]),
     "m1_focal_fwd": (_i, [_vp, _vp, _i, C.POINTER(_f), _f, _i, _ll, _i, _i, _vp, _vp, _vp]),
     "m1_focal_bwd": (_i, [_vp, _vp, _i, C.POINTER(_f), _f, _i, _ll, _i, _i, _vp, _vp, _vp]),

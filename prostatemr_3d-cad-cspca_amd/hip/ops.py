@@ -995,6 +995,73 @@ def tta_views(x: torch.Tensor, views) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Sliding-window inference: tiles of the network's size out of a larger volume and back (tile.hip; unets.networks.predict_tiled)
+# ---------------------------------------------------------------------------------------------------------
+def tile_struct(geom) -> L.m1_tile_t:
+    """m1_tile_t from ``tiling.tile_geometry``'s dict (an m1_tile_t passes through).  The C entry points check what it holds."""
+    if isinstance(geom, L.m1_tile_t):
+        return geom
+    g = L.m1_tile_t()
+    for a in range(3):
+        o = [int(v) for v in geom["origin"][a]]
+        if len(o) != int(geom["n"][a]) or not 1 <= len(o) <= L.M1_TILE_MAX_AXIS:
+            raise RuntimeError(f"tile geometry: axis {a} lists {len(o)} origins for n = {geom['n'][a]} (1..{L.M1_TILE_MAX_AXIS})")
+        g.vol[a], g.tile[a], g.n[a] = int(geom["vol"][a]), int(geom["tile"][a]), len(o)
+        for k, v in enumerate(o):
+            g.origin[a][k] = v
+    return g
+
+
+def tile_gather(x: torch.Tensor, geom) -> torch.Tensor:
+    """(T*B, d, h, w, C), tile-major (sample t * B + b is tile t of batch entry b): the tiles of ``geom`` (``tiling.tile_geometry``) cut
+    out of ``x`` (B, D, H, W, C) fp32 / bf16 (m1_tile_gather) -- the slices and their ``cat`` in one launch."""
+    _no_grad_only("tile_gather")
+    g = tile_struct(geom)
+    if x.dim() != 5 or tuple(int(v) for v in x.shape[1:4]) != tuple(g.vol):
+        raise RuntimeError(f"tile_gather: x must be (B, {', '.join(str(v) for v in g.vol)}, C), got {tuple(x.shape)}")
+    _req(x)
+    B, Cn = int(x.shape[0]), int(x.shape[4])
+    T = g.n[0] * g.n[1] * g.n[2]
+    out = torch.empty((T * B, *g.tile, Cn), dtype=x.dtype, device=x.device)
+    L.check(L.load().m1_tile_gather(_p(x), B, Cn, _dt(x), C.byref(g), _p(out), _stream()), "m1_tile_gather")
+    return out
+
+
+def tile_profile(weights, device) -> torch.Tensor:
+    """The three weight rows of a blend (``tiling.tile_weights``: host arrays) as the one fp32 device tensor m1_tile_blend reads, w0,
+    w1, w2 one after the other.  ValueError for an entry that is not finite and positive: the kernel divides by their sum."""
+    rows = [torch.as_tensor(r, dtype=torch.float32, device="cpu").reshape(-1) for r in weights]
+    if len(rows) != 3 or any(r.numel() < 1 for r in rows):
+        raise ValueError(f"tile_profile: three non-empty weight rows expected, got {[r.numel() for r in rows]}")
+    flat = torch.cat(rows)
+    if not bool((torch.isfinite(flat) & (flat > 0)).all()):
+        raise ValueError("tile_profile: every weight must be finite and > 0")
+    return flat.to(device)
+
+
+def tile_blend(tiles: torch.Tensor, geom, profile) -> torch.Tensor:
+    """(B, D, H, W, C) fp32: the weighted mean, voxel by voxel, of the tiles that cover it (m1_tile_blend).  ``tiles`` (T*B, d, h, w,
+    C) fp32 in ``tile_gather``'s order; ``profile``: the three host rows of ``tiling.tile_weights`` (checked and uploaded here), or the
+    device tensor ``tile_profile`` made of them (for a call that is captured or repeated)."""
+    _no_grad_only("tile_blend")
+    g = tile_struct(geom)
+    T = g.n[0] * g.n[1] * g.n[2]
+    if tiles.dim() != 5 or tiles.dtype != torch.float32 or tiles.shape[0] % T or tuple(int(v) for v in tiles.shape[1:4]) != tuple(g.tile):
+        raise RuntimeError(f"tile_blend: tiles must be fp32 ({T} * B, {', '.join(str(v) for v in g.tile)}, C), got {tiles.dtype} "
+                           f"{tuple(tiles.shape)}")
+    if not isinstance(profile, torch.Tensor):
+        profile = tile_profile(profile, tiles.device)
+    if profile.dtype != torch.float32 or profile.dim() != 1 or profile.numel() != sum(g.tile):
+        raise RuntimeError(f"tile_blend: profile must be fp32 ({sum(g.tile)},) = w0, w1, w2 of the tile {tuple(g.tile)}, got "
+                           f"{profile.dtype} {tuple(profile.shape)}")
+    _req(tiles, profile)
+    B, Cn = int(tiles.shape[0]) // T, int(tiles.shape[4])
+    out = torch.empty((B, *g.vol, Cn), dtype=torch.float32, device=tiles.device)
+    L.check(L.load().m1_tile_blend(_p(tiles), B, Cn, C.byref(g), _p(profile), _p(out), _stream()), "m1_tile_blend")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Per-case scoring of a validation batch (validate.hip; validation.validate)
 # ---------------------------------------------------------------------------------------------------------
 def val_score_ws(B: int, voxels: int, K: int) -> int:

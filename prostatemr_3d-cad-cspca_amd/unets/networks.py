@@ -1013,8 +1013,24 @@ class M1(LoadableModel):
                 res = _mc_results(sums, draws, N, uncertainty)
                 return res if outer.references.cascaded != False else res[0]  # noqa: E712
 
+            def predict_tiled(self, x, n_draws=1, draws_per_pass=1, tiles_per_pass=1, overlap=0.5, weighting='gaussian',
+                              uncertainty=False, tta=None):
+                """``predict`` / ``predict_mc`` of an ``x`` (B,D,H,W,C) whose every extent is at least the model's: sliding-window
+                inference, see ``_predict_tiled``, which ``Ensemble`` shares.  Returns what ``predict`` (n_draws == 1 without
+                ``uncertainty``: the mean tensor) or ``predict_mc`` (the dict) returns, on x's grid.  A cascaded model raises
+                NotImplementedError: its second stage reads the first stage's softmax tile by tile, and blending that is not built."""
+                if outer.references.cascaded != False:  # noqa: E712
+                    raise NotImplementedError(f"predict_tiled: cascaded models ('{outer.references.cascaded}') are not supported; only "
+                                              "single-stage models are")
+
+                def group(xg, n, R, unc, advance, views):
+                    return self._mc_passes(xg, n, R, unc, advance=advance, views=views)[0][0]
+                return _predict_tiled(group, 1, outer.input_spatial_dims, x, n_draws, draws_per_pass, tiles_per_pass, overlap, weighting,
+                                      uncertainty, tta)
+
             def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
-                             uncertainty=False, tta=None, **prepare_kw):
+                             uncertainty=False, tta=None, region=None, tiles_per_pass=1, overlap=0.5, weighting='gaussian',
+                             **prepare_kw):
                 """From a raw scan to a prediction on the scan's own grid: preprocess.prepare_scan to the model's input size, ``predict``
                 (n_draws == 1) or ``predict_mc``, then preprocess.restore of the result.  ``raw``: (B,d,h,w,C) fp32 / int16 on the
                 device at ``spacing`` (cascaded: the pair or dict of the two stages' scans, both on one grid); ``prepare_kw`` goes to
@@ -1024,10 +1040,14 @@ class M1(LoadableModel):
                 cascaded model returns [stage 1, stage 2] of these.  ``uncertainty``: the call goes through ``predict_mc(...,
                 uncertainty=True)`` even with one draw, and the result gains "expected_entropy" and "mutual_info" (B,d,h,w), restored
                 as the entropy is, and "variance" (B,d,h,w,nsel), restored with the channel selection of the mean.  ``tta`` goes to
-                ``predict`` / ``predict_mc``.  Host composition only (``_predict_scan``, shared with ``Ensemble``)."""
+                ``predict`` / ``predict_mc``.  ``region`` = (D,H,W) voxels at ``out_spacing``: the scan is prepared to max(region,
+                the model's size) per axis instead of the model's size, ``predict_tiled`` (with ``tiles_per_pass``, ``overlap``,
+                ``weighting``) stands in the middle, and "network" is on that larger grid; ``region=None`` is the call without it.
+                Host composition only (``_predict_scan``, shared with ``Ensemble``)."""
                 casc = outer.references.cascaded != False  # noqa: E712
                 return _predict_scan(self, outer.input_spatial_dims, outer._cascade_inputs if casc else None, raw, spacing, out_spacing,
-                                     n_draws, draws_per_pass, percentile, channels, labels, uncertainty, prepare_kw, tta)
+                                     n_draws, draws_per_pass, percentile, channels, labels, uncertainty, prepare_kw, tta, region,
+                                     tiles_per_pass, overlap, weighting)
         return _Detect()
 
     # ---- networks.py:209-223 ---------------------------------------------------------------------------------
@@ -1164,12 +1184,71 @@ def _mc_results(sums, draws, n, uncertainty):
     return res
 
 
+def _predict_tiled(group, members, dims, x, n_draws, draws_per_pass, tiles_per_pass, overlap, weighting, uncertainty, tta):
+    """Sliding-window inference of anything that runs MC passes on the network's grid ``dims``: ``x`` (B,D,H,W,C), every extent >=
+    ``dims`` (ValueError otherwise), is cut by ops.tile_gather into the T overlapping tiles of ``tiling.tile_geometry(x's grid, dims,
+    overlap)``; groups of ``tiles_per_pass`` consecutive tiles (it must divide T), stacked along the batch axis as the gather left
+    them, go through ``group(xg, n, R, uncertainty, advance, views)`` -> the group's accumulators (sum_p, or the triple with
+    ``uncertainty``) after all its draws: the detect model's ``_mc_passes``, or for an ``Ensemble`` (``members`` > 1) its members one
+    after the other with the carry it always uses.  The MC accumulators are linear in the draws, so it is THEY that are blended: each
+    group's accumulators are copied into their rows of one buffer per accumulator, allocated once for all T * B tiles (no ``cat``),
+    ops.tile_blend turns each buffer into the accumulator on x's grid -- a mean over the covering tiles with the separable weight
+    ``tiling.tile_weights(dims, weighting)``, 'gaussian' or 'constant' -- and one ops.mc_finalize finishes them.  What the tiles of a
+    voxel disagree on therefore lands in mutual_info and variance, as the disagreement between folds does in ``Ensemble``.
+    Draws and state: n_draws == 1 without ``uncertainty`` is ``predict`` -- one draw (with ``tta`` one stacked pass of the views) per
+    group at the current {seed, step} state, which does not move, and the mean tensor is returned.  Anything else is ``predict_mc``:
+    every group takes its own n_draws (times views) draws in passes of ``draws_per_pass`` and the state advances once per pass, group
+    after group in ascending tile order, (T / tiles_per_pass) * passes steps in all; the dict is returned.  The in-kernel draws are keyed
+    by the element index over the stacked batch, so the tiles of a group draw for themselves.  With T == 1 the one group is x itself:
+    the result and the state after the call are those of ``predict`` / ``predict_mc``, bit for bit."""
+    from .. import tiling
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise ValueError("predict_tiled: a tensor (B,D,H,W,C) expected (cascaded inputs are not supported)")
+    vol = tuple(int(v) for v in x.shape[1:4])
+    if any(v < d for v, d in zip(vol, dims)):
+        raise ValueError(f"predict_tiled: every extent of x must be at least the model's {tuple(dims)}, got {vol}")
+    views = tta_views(tta)
+    nv = len(views) if views else 1
+    single = int(n_draws) == 1 and not uncertainty
+    n, R = (1, nv) if single else _mc_counts(n_draws, draws_per_pass, views)
+    geom = tiling.tile_geometry(vol, dims, overlap)
+    weights = tiling.tile_weights(dims, weighting)
+    T, G, B = geom["T"], int(tiles_per_pass), int(x.shape[0])
+    if G < 1 or T % G:
+        raise ValueError(f"predict_tiled: tiles_per_pass must divide the {T} tiles of {vol} cut into {tuple(dims)}, got {tiles_per_pass}")
+    with torch.no_grad():
+        profile = ops.tile_profile(weights, x.device)
+        tiles = ops.tile_gather(x.contiguous(), geom)
+        bufs = None
+        for k in range(T // G):
+            rows = slice(k * G * B, (k + 1) * G * B)
+            sums = group(tiles[rows], n, R, uncertainty, not single, views)
+            parts = tuple(sums) if uncertainty else (sums,)
+            if bufs is None:
+                bufs = [torch.empty((T * B, *p.shape[1:]), dtype=torch.float32, device=p.device) for p in parts]
+            for buf, p in zip(bufs, parts):
+                buf[rows].copy_(p)
+        # (sum_h has no channel axis: it is blended as C = 1)
+        acc = [ops.tile_blend(b if b.dim() == 5 else b.unsqueeze(-1), geom, profile) for b in bufs]
+        acc = [a if b.dim() == 5 else a.squeeze(-1) for a, b in zip(acc, bufs)]
+        res = ops.mc_finalize(tuple(acc) if uncertainty else acc[0], members * n * nv, uncertainty)
+    return res["mean"] if single else res
+
+
 def _predict_scan(predictor, dims, cascade_inputs, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile, channels, labels,
-                  uncertainty, prepare_kw, tta=None):
+                  uncertainty, prepare_kw, tta=None, region=None, tiles_per_pass=1, overlap=0.5, weighting='gaussian'):
     """``predict_scan`` of anything with ``predict`` / ``predict_mc``: prepare_scan to the network's grid ``dims``, the prediction,
-    preprocess.restore of every map.  ``cascade_inputs``: the cascaded model's splitter of ``raw`` into its two scans, else None."""
+    preprocess.restore of every map.  ``cascade_inputs``: the cascaded model's splitter of ``raw`` into its two scans, else None.
+    ``region``: prepare_scan to max(region, dims) per axis and ``predict_tiled`` as the prediction (restore reads the grid off the
+    map it is given)."""
     from .. import preprocess as PP
     casc = cascade_inputs is not None
+    if region is not None:
+        if casc:
+            raise NotImplementedError("predict_scan: region needs predict_tiled, which cascaded models do not have")
+        if len(tuple(region)) != 3 or any(int(v) < 1 for v in region):
+            raise ValueError(f"predict_scan: region must be three positive extents (D, H, W), got {region}")
+        dims = tuple(max(int(r), int(d)) for r, d in zip(region, dims))
     raws = list(cascade_inputs(raw)) if casc else [raw]
     shape = tuple(int(v) for v in raws[0].shape[1:4])
     if any(tuple(int(v) for v in r.shape[1:4]) != shape for r in raws):
@@ -1177,7 +1256,9 @@ def _predict_scan(predictor, dims, cascade_inputs, raw, spacing, out_spacing, n_
     xs = [PP.prepare_scan(r, spacing, out_spacing, dims, percentile=percentile, **prepare_kw)[0] for r in raws]
     x = xs if casc else xs[0]
     kw = {} if tta is None else {"tta": tta}
-    if uncertainty:
+    if region is not None:
+        net = predictor.predict_tiled(x, n_draws, draws_per_pass, tiles_per_pass, overlap, weighting, uncertainty, tta)
+    elif uncertainty:
         net = predictor.predict_mc(x, n_draws, draws_per_pass, uncertainty=True, **kw)
     else:
         net = predictor.predict(x, **kw) if int(n_draws) == 1 else predictor.predict_mc(x, n_draws, draws_per_pass, **kw)
@@ -1274,8 +1355,18 @@ class Ensemble:
         sums, draws = self._fold(x, n, R, uncertainty, return_samples, views=views)
         return _mc_results(sums, draws, len(self.detectors) * n * (len(views) if views else 1), uncertainty)[0]
 
+    def predict_tiled(self, x, n_draws=1, draws_per_pass=1, tiles_per_pass=1, overlap=0.5, weighting='gaussian', uncertainty=False,
+                      tta=None):
+        """``predict_tiled`` of the detect model (``_predict_tiled``) over N = members * n_draws draws per tile: every group of tiles
+        goes member by member into one set of accumulators, each member drawing from its own state as in its own call."""
+        def group(xg, n, R, unc, advance, views):
+            return self._fold(xg, n, R, unc, False, advance=advance, views=views)[0][0]
+        return _predict_tiled(group, len(self.detectors), self.input_spatial_dims, x, n_draws, draws_per_pass, tiles_per_pass, overlap,
+                              weighting, uncertainty, tta)
+
     def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
-                     uncertainty=False, tta=None, **prepare_kw):
-        """``predict_scan`` of the detect model, with this ensemble's ``predict`` / ``predict_mc`` in the middle."""
+                     uncertainty=False, tta=None, region=None, tiles_per_pass=1, overlap=0.5, weighting='gaussian', **prepare_kw):
+        """``predict_scan`` of the detect model, with this ensemble's ``predict`` / ``predict_mc`` (``predict_tiled`` with ``region``)
+        in the middle."""
         return _predict_scan(self, self.input_spatial_dims, None, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile,
-                             channels, labels, uncertainty, prepare_kw, tta)
+                             channels, labels, uncertainty, prepare_kw, tta, region, tiles_per_pass, overlap, weighting)
