@@ -1,6 +1,6 @@
 """Sliding-window inference, host side: where the tiles of a fixed-size network go on a larger volume, the separable weight they are
 blended with, and fp64 restatements of the two kernels of csrc/tile.hip (m1_tile_gather / m1_tile_blend, ``ops.tile_gather`` /
-``ops.tile_blend``).  ``unets.networks.predict_tiled`` is the public surface; nothing here touches the GPU.
+``ops.tile_blend``).  ``predict_tiled`` of the detect model and of ``Ensemble`` (``unets.inference``) is the public surface; nothing here touches the GPU.
 
 Tiles never leave the volume: an axis of length L takes n tiles of length t at evenly spread origins from 0 to L - t, so the last tile
 ends at L and nothing is padded.  Tile t = (i0 * n[1] + i1) * n[2] + i2, and a stack of tiles is tile-major: sample t * B + b is tile t

@@ -855,7 +855,7 @@ class M1(LoadableModel):
     def forward(self, x, training: Optional[bool] = None, eps_q=None):
         """``eps_q``: optional injected N(0,1) draws of the posterior's latent samples (cascaded: one list per stage)."""
         if self.references.cascaded != False:  # noqa: E712
-            return self._forward_cascaded(x, eps_q=eps_q)
+            return self._cascade_outputs(*self._cascade_stages(x, eps_q=eps_q))
         o = self.m1_model(self._prep(x), eps_q=eps_q)
         if self.references.probabilistic:
             return [o['prob_softmax'], o['prob_kl']]
@@ -873,20 +873,23 @@ class M1(LoadableModel):
         prior_in = p1[..., :nc - 1].to(self.compute_dtype)
         return torch.cat([prior_in, self._prep(x2, channels=self.input_channels)], dim=-1).contiguous()
 
-    def _forward_cascaded(self, x, eps_q=None, eps_p=None, with_infer=False):
-        """networks.py:109-193.  Stage 2 sees cat[stage-1 softmax[..., :nc-1], image_2]; fusion per decision_fusion.
-        Returns [detection_1, detection_2 (, KL_1, KL_2)] (networks.py:168-171,181-182)."""
+    def _cascade_stages(self, x, eps_q=None, eps_p=None, with_infer=False):
+        """networks.py:109-153.  Runs the two stages, stage 2 on cat[stage-1 softmax[..., :nc-1], image_2]; returns their output dicts
+        (o1, o2)."""
         x1, x2 = self._cascade_inputs(x)
-        nc, prob = self.num_classes, self.references.probabilistic
-        key = 'prob_softmax' if prob else 'y_softmax'
+        key = 'prob_softmax' if self.references.probabilistic else 'y_softmax'
         e_q = eps_q if eps_q is not None else (None, None)
         e_p = eps_p if eps_p is not None else (None, None)
         o1 = self.m1_stage1(self._prep(x1, channels=self.input_channels), eps_q=e_q[0], eps_p=e_p[0], with_infer=with_infer)
-        p1 = o1[key]
-        o2 = self.m1_stage2(self._stage2_input(p1, x2), eps_q=e_q[1], eps_p=e_p[1], with_infer=with_infer)
-        p2 = o2[key]
-        prior_pred, joint_pred = self.decision_fusion(p1[..., nc - 1], p2[..., nc - 1], strategy=self.references.cascaded)
-        self._last_cascade = (o1, o2)
+        o2 = self.m1_stage2(self._stage2_input(o1[key], x2), eps_q=e_q[1], eps_p=e_p[1], with_infer=with_infer)
+        return o1, o2
+
+    def _cascade_outputs(self, o1, o2):
+        """networks.py:155-193.  Fusion per decision_fusion of the two stages' outputs -> [detection_1, detection_2 (, KL_1, KL_2)]
+        (networks.py:168-171,181-182)."""
+        nc, prob = self.num_classes, self.references.probabilistic
+        key = 'prob_softmax' if prob else 'y_softmax'
+        prior_pred, joint_pred = self.decision_fusion(o1[key][..., nc - 1], o2[key][..., nc - 1], strategy=self.references.cascaded)
         if prob:
             return [prior_pred, joint_pred, o1['prob_kl'], o2['prob_kl']]
         return [prior_pred, joint_pred]
@@ -900,155 +903,7 @@ class M1(LoadableModel):
         the stage-1 TRAINING softmax exactly as the reference's graph is wired (networks.py:135-136,174-175,199-200);
         deterministic -> [stage-1 y_softmax[..., :nc], stage-2 y_softmax[..., :nc]].
         ``eps_q`` / ``eps_p``: optional injected draws (tests), per stage when cascaded."""
-        outer = self
-
-        class _Detect(nn.Module):
-            def forward(self, x, eps_q=None, eps_p=None):
-                nc = outer.references.num_classes
-                prob = outer.references.probabilistic
-                with torch.no_grad():
-                    if outer.references.cascaded != False:  # noqa: E712
-                        if not prob:
-                            outer._forward_cascaded(x)
-                            o1, o2 = outer._last_cascade
-                            return [o1['y_softmax'][..., :nc], o2['y_softmax'][..., :nc]]
-                        outer._forward_cascaded(x, eps_q=eps_q, eps_p=eps_p, with_infer=True)
-                        o1, o2 = outer._last_cascade
-                        return [ops.softmax_heads([o1['prob_infer_conv']], [(1, 1, 1)]),
-                                ops.softmax_heads([o2['prob_infer_conv']], [(1, 1, 1)])]
-                    if prob:
-                        o = outer.m1_model(outer._prep(x), train_outputs=False, eps_p=eps_p)
-                        return ops.softmax_heads([o['prob_infer_conv']], [(1, 1, 1)])
-                    o = outer.m1_model(outer._prep(x))
-                    return o['y_softmax'][..., :nc]
-
-            def predict(self, x, tta=None, **kw):
-                """``forward``; with ``tta`` (see ``tta_views``) the mean over the mirrored views, each un-mirrored: what
-                ``predict_mc(x, 1, draws_per_pass=len(views), tta=views)`` returns as "mean" from the current state, one stacked pass.
-                The {seed, step} state does not move."""
-                views = tta_views(tta)
-                if views is None:
-                    return self.forward(x, **kw)
-                if kw.get("eps_q") is not None:
-                    raise ValueError("predict: eps_q has no part in a prediction with tta")
-                sums, _ = self._mc_passes(x, 1, len(views), eps_p=kw.get("eps_p"), advance=False, views=views)
-                means = [r["mean"] for r in _mc_results(sums, None, len(views), False)]
-                return means if outer.references.cascaded != False else means[0]  # noqa: E712
-
-            def _mc_passes(self, x, n, R, uncertainty=False, eps_p=None, carry=None, total=0, first=0, advance=True, views=None):
-                """``n // R`` passes of ``R`` replicas each, folded into the accumulators ``carry`` = (sums, draws) of an earlier call
-                (another model's, see ``Ensemble``) or into fresh ones; returns (sums, draws), one entry per stage.  sums[j] is
-                ops.mc_accumulate's sum_p, or its triple with ``uncertainty``.  ``total`` > 0 asks for the per-draw
-                probabilities: draws[j] is (total, B, D, H, W, nc), and this call fills [first, first + n).  The {seed, step} state
-                advances once per pass unless ``advance`` is False.
-                ``views`` (mirror masks, ``tta_views``): len(views) * n draws, view-major, in (len(views) * n) // R passes of R
-                consecutive draws; a pass's input is ops.tta_views of its draws' masks (both stages of a cascaded model alike) and
-                its logits go to ops.mc_accumulate with these masks, which un-mirrors them; the call fills
-                [first, first + len(views) * n)."""
-                prob = outer.references.probabilistic
-                casc = outer.references.cascaded != False  # noqa: E712
-                # (with views the stacks come from ops.tta_views, pass by pass)
-                rep = (lambda t: t.repeat(R, 1, 1, 1, 1)) if R > 1 and views is None else (lambda t: t)
-                sums, draws = carry if carry is not None else (None, None)
-                with torch.no_grad():
-                    if casc:
-                        x1, x2 = outer._cascade_inputs(x)
-                        xin = (rep(outer._prep(x1, channels=outer.input_channels)), rep(outer._prep(x2, channels=outer.input_channels)))
-                    else:
-                        xin = rep(outer._prep(x))
-                    base, mirrored, passes = xin, {}, (n if views is None else len(views) * n) // R
-                    for k in range(passes):
-                        masks = None if views is None else tuple(views[j // n] for j in range(k * R, (k + 1) * R))
-                        if masks is not None:
-                            if masks not in mirrored:
-                                mirrored[masks] = tuple(ops.tta_views(t, masks) for t in base) if casc else ops.tta_views(base, masks)
-                            xin = mirrored[masks]
-                        if casc:
-                            outer._forward_cascaded(xin, eps_p=eps_p, with_infer=prob)
-                            outs = outer._last_cascade
-                        else:
-                            outs = (outer.m1_model(xin, train_outputs=False, eps_p=eps_p) if prob else outer.m1_model(xin),)
-                        logits = [o['prob_infer_conv'] if prob else o['logits'] for o in outs]
-                        if sums is None:
-                            sums = [None] * len(logits)
-                        if total and draws is None:
-                            draws = [torch.empty((total, int(l.shape[0]) // R, *l.shape[1:]), dtype=torch.float32, device=l.device)
-                                     for l in logits]
-                        for j, l in enumerate(logits):
-                            lo = first + k * R
-                            r = ops.mc_accumulate(l, R, sums[j], draws[j][lo:lo + R] if total else False, uncertainty, masks)
-                            sums[j] = r[0] if total else r
-                        if advance:
-                            outer.advance_rng()
-                return sums, draws
-
-            def predict_mc(self, x, n_draws, draws_per_pass=1, return_samples=False, eps_p=None, uncertainty=False, tta=None):
-                """Monte-Carlo inference (the reference's --UNET_PROBA_ITER, train_model.py:72): ``n_draws`` hypotheses of ``predict`` --
-                fresh dropout masks and, for the probabilistic model, fresh z ~ P at every level -- folded into
-                {"mean": (B,D,H,W,nc) fp32, "entropy": (B,D,H,W) fp32 in nats (scipy.stats.entropy of the mean)
-                 [, "samples": (n_draws,B,D,H,W,nc) fp32 with ``return_samples``]}; a cascaded model returns [stage 1, stage 2] of these.
-                A pass runs ``draws_per_pass`` replicas of the input stacked along the batch axis, replica-major (sample r*B + b is
-                replica r of sample b): the in-kernel draws are keyed by the element index over the whole batch, so every replica
-                draws for itself.  The head's raw logits go to ops.mc_accum, which keeps only the running sum of the probabilities;
-                ops.mc_finish divides and takes the entropy.  The {seed, step} state advances once per pass: the first draw is what
-                ``predict(x)`` returns at the current state, and the call leaves the state at step + n_draws / draws_per_pass.
-                ``eps_p`` (injected draws, as in ``forward``) only with n_draws == 1: every draw would be the same.
-                ``uncertainty``: the passes go through ops.mc_accum_u / ops.mc_finish_u and the result gains, per voxel and in nats,
-                "expected_entropy" (B,D,H,W) = the mean of the draws' own entropies (what every draw agrees is ambiguous),
-                "mutual_info" (B,D,H,W) = entropy - expected_entropy >= 0 (what the draws disagree on) and "variance" (B,D,H,W,nc),
-                the population variance of the draws per class.  mean, entropy, samples and the state after the call are those of
-                the call without it; one draw gives mutual_info = variance = +0.
-                ``tta`` (see ``tta_views``): test-time augmentation by mirroring.  Every view takes ``n_draws`` draws, N = views *
-                n_draws in all, view-major (view v owns draws [v * n_draws, (v + 1) * n_draws)), cut into passes of ``draws_per_pass``
-                consecutive draws, which must divide N; a pass may mix views.  The input of a pass is ops.tta_views, its logits go
-                to ops.mc_accum_v, which reads them at the mirrored coordinates: the sums, the maps and the samples (N,B,D,H,W,nc)
-                are on the caller's grid, and no un-mirrored tensor exists in between.  ``tta=None`` is the call without it;
-                ``tta=("",)`` gives its bits and its final state."""
-                views = tta_views(tta)
-                n, R = _mc_counts(n_draws, draws_per_pass, views)
-                N = n * (len(views) if views else 1)
-                if eps_p is not None and N > 1:
-                    raise ValueError("predict_mc: injected eps_p with n_draws > 1 would repeat one draw n_draws times")
-                sums, draws = self._mc_passes(x, n, R, uncertainty, eps_p, total=N if return_samples else 0, views=views)
-                res = _mc_results(sums, draws, N, uncertainty)
-                return res if outer.references.cascaded != False else res[0]  # noqa: E712
-
-            def predict_tiled(self, x, n_draws=1, draws_per_pass=1, tiles_per_pass=1, overlap=0.5, weighting='gaussian',
-                              uncertainty=False, tta=None):
-                """``predict`` / ``predict_mc`` of an ``x`` (B,D,H,W,C) whose every extent is at least the model's: sliding-window
-                inference, see ``_predict_tiled``, which ``Ensemble`` shares.  Returns what ``predict`` (n_draws == 1 without
-                ``uncertainty``: the mean tensor) or ``predict_mc`` (the dict) returns, on x's grid.  A cascaded model raises
-                NotImplementedError: its second stage reads the first stage's softmax tile by tile, and blending that is not built."""
-                if outer.references.cascaded != False:  # noqa: E712
-                    raise NotImplementedError(f"predict_tiled: cascaded models ('{outer.references.cascaded}') are not supported; only "
-                                              "single-stage models are")
-
-                def group(xg, n, R, unc, advance, views):
-                    return self._mc_passes(xg, n, R, unc, advance=advance, views=views)[0][0]
-                return _predict_tiled(group, 1, outer.input_spatial_dims, x, n_draws, draws_per_pass, tiles_per_pass, overlap, weighting,
-                                      uncertainty, tta)
-
-            def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
-                             uncertainty=False, tta=None, region=None, tiles_per_pass=1, overlap=0.5, weighting='gaussian',
-                             **prepare_kw):
-                """From a raw scan to a prediction on the scan's own grid: preprocess.prepare_scan to the model's input size, ``predict``
-                (n_draws == 1) or ``predict_mc``, then preprocess.restore of the result.  ``raw``: (B,d,h,w,C) fp32 / int16 on the
-                device at ``spacing`` (cascaded: the pair or dict of the two stages' scans, both on one grid); ``prepare_kw`` goes to
-                prepare_scan (pad_mode, constant_values, dtype, default_value).  Returns {"mean": (B,d,h,w,nsel) fp32, the channels
-                ``channels`` of the restored softmax [, "entropy": (B,d,h,w) with n_draws > 1] [, "labels": (B,d,h,w) uint8, the argmax
-                of the restored softmax, with ``labels``], "network": what predict / predict_mc returned on the network's grid}; a
-                cascaded model returns [stage 1, stage 2] of these.  ``uncertainty``: the call goes through ``predict_mc(...,
-                uncertainty=True)`` even with one draw, and the result gains "expected_entropy" and "mutual_info" (B,d,h,w), restored
-                as the entropy is, and "variance" (B,d,h,w,nsel), restored with the channel selection of the mean.  ``tta`` goes to
-                ``predict`` / ``predict_mc``.  ``region`` = (D,H,W) voxels at ``out_spacing``: the scan is prepared to max(region,
-                the model's size) per axis instead of the model's size, ``predict_tiled`` (with ``tiles_per_pass``, ``overlap``,
-                ``weighting``) stands in the middle, and "network" is on that larger grid; ``region=None`` is the call without it.
-                Host composition only (``_predict_scan``, shared with ``Ensemble``)."""
-                casc = outer.references.cascaded != False  # noqa: E712
-                return _predict_scan(self, outer.input_spatial_dims, outer._cascade_inputs if casc else None, raw, spacing, out_spacing,
-                                     n_draws, draws_per_pass, percentile, channels, labels, uncertainty, prepare_kw, tta, region,
-                                     tiles_per_pass, overlap, weighting)
-        return _Detect()
+        return Detector(self)
 
     # ---- networks.py:209-223 ---------------------------------------------------------------------------------
     def decision_fusion(self, prior_softmax, follow_up_softmax, strategy='identity'):
@@ -1124,249 +979,5 @@ class M1(LoadableModel):
         return logs
 
 
-# ============================================================================================================
-# Monte-Carlo inference: what the detect model and an ensemble of detect models share (host composition only)
-# ============================================================================================================
-def _mc_counts(n_draws, draws_per_pass, views=None):
-    n, R = int(n_draws), int(draws_per_pass)
-    if views is not None:
-        if n < 1 or R < 1 or (len(views) * n) % R:
-            raise ValueError(f"predict_mc: n_draws >= 1 and draws_per_pass dividing views * n_draws = {len(views) * n} expected, got "
-                             f"{n_draws} / {draws_per_pass}")
-        if R > 16:
-            raise ValueError(f"predict_mc: at most 16 draws per pass with tta (one mirror mask each), got {R}")
-        return n, R
-    if n < 1 or R < 1 or n % R:
-        raise ValueError(f"predict_mc: n_draws >= 1 and draws_per_pass dividing it expected, got {n_draws} / {draws_per_pass}")
-    return n, R
-
-
-_TTA_BITS = {"w": 1, "h": 2, "d": 4}
-
-
-def tta_views(spec):
-    """The mirror masks of a test-time augmentation: ``None`` (no TTA) or a non-empty sequence of views, each a string over the letters
-    ``d``, ``h``, ``w`` naming the axes it mirrors (``""`` or ``"id"``: the identity), e.g. ``("", "w")`` or ``("", "w", "h", "hw")``
-    -> the tuple of 3-bit masks (w = 1, h = 2, d = 4) that ops.tta_views / ops.mc_accum_v take.  The identity is a view like any
-    other: it is in only if listed.  ValueError for an unknown or repeated letter, a view listed twice, or no view at all."""
-    if spec is None:
-        return None
-    if isinstance(spec, str):
-        raise ValueError(f"tta: a sequence of views expected, e.g. ('', 'w'), got the string {spec!r}")
-    masks = []
-    for v in spec:
-        if isinstance(v, str):
-            letters = "" if v == "id" else v.lower()
-            if any(c not in _TTA_BITS for c in letters) or len(set(letters)) != len(letters):
-                raise ValueError(f"tta: a view is made of the letters d, h, w, each at most once ('' or 'id': identity), got {v!r}")
-            m = sum(_TTA_BITS[c] for c in letters)
-        elif isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= int(v) <= 7:
-            m = int(v)
-        else:
-            raise ValueError(f"tta: a view is a string over d, h, w (or its mask 0..7), got {v!r}")
-        if m in masks:
-            raise ValueError(f"tta: view {v!r} is listed twice")
-        masks.append(m)
-    if not masks:
-        raise ValueError("tta: at least one view expected (None switches it off)")
-    return tuple(masks)
-
-
-def _mc_results(sums, draws, n, uncertainty):
-    """The accumulators of ``_mc_passes`` after ``n`` draws in all -> one result dict per stage."""
-    res = []
-    with torch.no_grad():
-        for j, s in enumerate(sums):
-            d = ops.mc_finalize(s, n, uncertainty)
-            if draws is not None:
-                d["samples"] = draws[j]
-            res.append(d)
-    return res
-
-
-def _predict_tiled(group, members, dims, x, n_draws, draws_per_pass, tiles_per_pass, overlap, weighting, uncertainty, tta):
-    """Sliding-window inference of anything that runs MC passes on the network's grid ``dims``: ``x`` (B,D,H,W,C), every extent >=
-    ``dims`` (ValueError otherwise), is cut by ops.tile_gather into the T overlapping tiles of ``tiling.tile_geometry(x's grid, dims,
-    overlap)``; groups of ``tiles_per_pass`` consecutive tiles (it must divide T), stacked along the batch axis as the gather left
-    them, go through ``group(xg, n, R, uncertainty, advance, views)`` -> the group's accumulators (sum_p, or the triple with
-    ``uncertainty``) after all its draws: the detect model's ``_mc_passes``, or for an ``Ensemble`` (``members`` > 1) its members one
-    after the other with the carry it always uses.  The MC accumulators are linear in the draws, so it is THEY that are blended: each
-    group's accumulators are copied into their rows of one buffer per accumulator, allocated once for all T * B tiles (no ``cat``),
-    ops.tile_blend turns each buffer into the accumulator on x's grid -- a mean over the covering tiles with the separable weight
-    ``tiling.tile_weights(dims, weighting)``, 'gaussian' or 'constant' -- and one ops.mc_finalize finishes them.  What the tiles of a
-    voxel disagree on therefore lands in mutual_info and variance, as the disagreement between folds does in ``Ensemble``.
-    Draws and state: n_draws == 1 without ``uncertainty`` is ``predict`` -- one draw (with ``tta`` one stacked pass of the views) per
-    group at the current {seed, step} state, which does not move, and the mean tensor is returned.  Anything else is ``predict_mc``:
-    every group takes its own n_draws (times views) draws in passes of ``draws_per_pass`` and the state advances once per pass, group
-    after group in ascending tile order, (T / tiles_per_pass) * passes steps in all; the dict is returned.  The in-kernel draws are keyed
-    by the element index over the stacked batch, so the tiles of a group draw for themselves.  With T == 1 the one group is x itself:
-    the result and the state after the call are those of ``predict`` / ``predict_mc``, bit for bit."""
-    from .. import tiling
-    if not isinstance(x, torch.Tensor) or x.dim() != 5:
-        raise ValueError("predict_tiled: a tensor (B,D,H,W,C) expected (cascaded inputs are not supported)")
-    vol = tuple(int(v) for v in x.shape[1:4])
-    if any(v < d for v, d in zip(vol, dims)):
-        raise ValueError(f"predict_tiled: every extent of x must be at least the model's {tuple(dims)}, got {vol}")
-    views = tta_views(tta)
-    nv = len(views) if views else 1
-    single = int(n_draws) == 1 and not uncertainty
-    n, R = (1, nv) if single else _mc_counts(n_draws, draws_per_pass, views)
-    geom = tiling.tile_geometry(vol, dims, overlap)
-    weights = tiling.tile_weights(dims, weighting)
-    T, G, B = geom["T"], int(tiles_per_pass), int(x.shape[0])
-    if G < 1 or T % G:
-        raise ValueError(f"predict_tiled: tiles_per_pass must divide the {T} tiles of {vol} cut into {tuple(dims)}, got {tiles_per_pass}")
-    with torch.no_grad():
-        profile = ops.tile_profile(weights, x.device)
-        tiles = ops.tile_gather(x.contiguous(), geom)
-        bufs = None
-        for k in range(T // G):
-            rows = slice(k * G * B, (k + 1) * G * B)
-            sums = group(tiles[rows], n, R, uncertainty, not single, views)
-            parts = tuple(sums) if uncertainty else (sums,)
-            if bufs is None:
-                bufs = [torch.empty((T * B, *p.shape[1:]), dtype=torch.float32, device=p.device) for p in parts]
-            for buf, p in zip(bufs, parts):
-                buf[rows].copy_(p)
-        # (sum_h has no channel axis: it is blended as C = 1)
-        acc = [ops.tile_blend(b if b.dim() == 5 else b.unsqueeze(-1), geom, profile) for b in bufs]
-        acc = [a if b.dim() == 5 else a.squeeze(-1) for a, b in zip(acc, bufs)]
-        res = ops.mc_finalize(tuple(acc) if uncertainty else acc[0], members * n * nv, uncertainty)
-    return res["mean"] if single else res
-
-
-def _predict_scan(predictor, dims, cascade_inputs, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile, channels, labels,
-                  uncertainty, prepare_kw, tta=None, region=None, tiles_per_pass=1, overlap=0.5, weighting='gaussian'):
-    """``predict_scan`` of anything with ``predict`` / ``predict_mc``: prepare_scan to the network's grid ``dims``, the prediction,
-    preprocess.restore of every map.  ``cascade_inputs``: the cascaded model's splitter of ``raw`` into its two scans, else None.
-    ``region``: prepare_scan to max(region, dims) per axis and ``predict_tiled`` as the prediction (restore reads the grid off the
-    map it is given)."""
-    from .. import preprocess as PP
-    casc = cascade_inputs is not None
-    if region is not None:
-        if casc:
-            raise NotImplementedError("predict_scan: region needs predict_tiled, which cascaded models do not have")
-        if len(tuple(region)) != 3 or any(int(v) < 1 for v in region):
-            raise ValueError(f"predict_scan: region must be three positive extents (D, H, W), got {region}")
-        dims = tuple(max(int(r), int(d)) for r, d in zip(region, dims))
-    raws = list(cascade_inputs(raw)) if casc else [raw]
-    shape = tuple(int(v) for v in raws[0].shape[1:4])
-    if any(tuple(int(v) for v in r.shape[1:4]) != shape for r in raws):
-        raise ValueError(f"predict_scan: both stages' scans must share one grid, got {[tuple(r.shape) for r in raws]}")
-    xs = [PP.prepare_scan(r, spacing, out_spacing, dims, percentile=percentile, **prepare_kw)[0] for r in raws]
-    x = xs if casc else xs[0]
-    kw = {} if tta is None else {"tta": tta}
-    if region is not None:
-        net = predictor.predict_tiled(x, n_draws, draws_per_pass, tiles_per_pass, overlap, weighting, uncertainty, tta)
-    elif uncertainty:
-        net = predictor.predict_mc(x, n_draws, draws_per_pass, uncertainty=True, **kw)
-    else:
-        net = predictor.predict(x, **kw) if int(n_draws) == 1 else predictor.predict_mc(x, n_draws, draws_per_pass, **kw)
-    res = []
-    for o in (net if casc else [net]):
-        mean = o["mean"] if isinstance(o, dict) else o
-        r = PP.restore(mean.contiguous(), shape, spacing, out_spacing, order=1, channels=channels, labels=labels)
-        d = {"mean": r[0] if labels else r}
-        if isinstance(o, dict):
-            for k in ("entropy", "expected_entropy", "mutual_info"):
-                if k in o:
-                    d[k] = PP.restore(o[k].unsqueeze(-1), shape, spacing, out_spacing, order=1)[..., 0]
-            if "variance" in o:
-                d["variance"] = PP.restore(o["variance"].contiguous(), shape, spacing, out_spacing, order=1, channels=channels)
-        if labels:
-            d["labels"] = r[1]
-        d["network"] = o
-        res.append(d)
-    return res if casc else res[0]
-
-
-class Ensemble:
-    """Several non-cascaded ``M1`` models -- the trainer's one model per fold (--FOLDS 0 1 2 3 4) -- as one predictor.  An ensemble is
-    more draws into the same accumulators: every member's passes are folded by ops.mc_accum[_u] into the sums the previous member
-    left, in list order, and finished once with N = members * n_draws.  With ``uncertainty`` the between-draw term (mutual_info,
-    variance) therefore also carries the disagreement between the folds.
-    Each member draws from its own {seed, step} state, which advances exactly as that member's own ``predict_mc`` call would;
-    ``seed`` gives member i ``seed_dropout(seed + i)``.
-    ``Ensemble([m])`` equals ``m.get_detect_model()`` bit for bit from the same state.  The order of the members is the order of the
-    summation: ensembles of the same members in another order agree to rounding (the tests' bound), not to the bit."""
-
-    def __init__(self, models, seed=None):
-        models = list(models)
-        if not models:
-            raise ValueError("Ensemble: at least one model expected")
-        for i, m in enumerate(models):
-            if not isinstance(m, M1):
-                raise ValueError(f"Ensemble: member {i} is a {type(m).__name__}, not an M1")
-            if m.references.cascaded != False:  # noqa: E712
-                raise NotImplementedError(f"Ensemble: member {i} is a cascaded model ('{m.references.cascaded}'); only single-stage "
-                                          "members are supported")
-        for what in ("num_classes", "input_spatial_dims", "input_channels"):
-            vals = [getattr(m, what) for m in models]
-            if any(v != vals[0] for v in vals):
-                raise ValueError(f"Ensemble: members disagree in {what}: {vals}")
-        self.models = models
-        self.detectors = [m.get_detect_model() for m in models]
-        self.num_classes, self.input_spatial_dims = models[0].num_classes, models[0].input_spatial_dims
-        self.input_channels = models[0].input_channels
-        if seed is not None:
-            for i, m in enumerate(models):
-                m.seed_dropout(int(seed) + i)
-
-    @classmethod
-    def load(cls, paths, device, compute_dtype=None, seed=None):
-        """One member per entry of ``paths`` through ``M1.load``: a checkpoint file (model_weights_NNN.npz), or a fold directory, of
-        which the checkpoint with the highest number is taken.  Members are moved to ``device`` and put in eval mode."""
-        import glob
-        models = []
-        for p in paths:
-            if _os.path.isdir(p):
-                found = sorted(glob.glob(_os.path.join(p, "model_weights_*.npz")))
-                if not found:
-                    raise FileNotFoundError(f"Ensemble.load: no model_weights_*.npz in {p}")
-                p = found[-1]
-            m = M1.load(p).to(device)
-            if compute_dtype is not None:
-                m.set_compute_dtype(compute_dtype)
-            m.eval()
-            models.append(m)
-        return cls(models, seed=seed)
-
-    def _fold(self, x, n, R, uncertainty, samples, advance=True, views=None):
-        per = n * (len(views) if views else 1)                        # (draws per member)
-        carry, total = None, len(self.detectors) * per if samples else 0
-        for i, dm in enumerate(self.detectors):
-            carry = dm._mc_passes(x, n, R, uncertainty, carry=carry, total=total, first=i * per, advance=advance, views=views)
-        return carry
-
-    def predict(self, x, tta=None):
-        """(B,D,H,W,nc) fp32: the mean of the members' ``predict(x)``, one draw each at the member's current state (which does not
-        move, as in ``predict``); with ``tta`` the mean of the members' ``predict(x, tta=tta)``, one stacked pass per member."""
-        views = tta_views(tta)
-        nv = len(views) if views else 1
-        sums, _ = self._fold(x, 1, nv, False, False, advance=False, views=views)
-        return _mc_results(sums, None, len(self.detectors) * nv, False)[0]["mean"]
-
-    def predict_mc(self, x, n_draws, draws_per_pass=1, uncertainty=False, return_samples=False, tta=None):
-        """``predict_mc`` of the detect model over N = members * n_draws draws, ``n_draws`` per member; "samples" (N,B,D,H,W,nc) are
-        member-major (member i's draws at [i * n_draws, (i + 1) * n_draws)).  With ``tta``: N = members * views * n_draws, member-major,
-        then view-major, every member's passes cut as in its own ``predict_mc(..., tta=tta)``."""
-        views = tta_views(tta)
-        n, R = _mc_counts(n_draws, draws_per_pass, views)
-        sums, draws = self._fold(x, n, R, uncertainty, return_samples, views=views)
-        return _mc_results(sums, draws, len(self.detectors) * n * (len(views) if views else 1), uncertainty)[0]
-
-    def predict_tiled(self, x, n_draws=1, draws_per_pass=1, tiles_per_pass=1, overlap=0.5, weighting='gaussian', uncertainty=False,
-                      tta=None):
-        """``predict_tiled`` of the detect model (``_predict_tiled``) over N = members * n_draws draws per tile: every group of tiles
-        goes member by member into one set of accumulators, each member drawing from its own state as in its own call."""
-        def group(xg, n, R, unc, advance, views):
-            return self._fold(xg, n, R, unc, False, advance=advance, views=views)[0][0]
-        return _predict_tiled(group, len(self.detectors), self.input_spatial_dims, x, n_draws, draws_per_pass, tiles_per_pass, overlap,
-                              weighting, uncertainty, tta)
-
-    def predict_scan(self, raw, spacing, out_spacing, n_draws=1, draws_per_pass=1, percentile=None, channels=None, labels=False,
-                     uncertainty=False, tta=None, region=None, tiles_per_pass=1, overlap=0.5, weighting='gaussian', **prepare_kw):
-        """``predict_scan`` of the detect model, with this ensemble's ``predict`` / ``predict_mc`` (``predict_tiled`` with ``region``)
-        in the middle."""
-        return _predict_scan(self, self.input_spatial_dims, None, raw, spacing, out_spacing, n_draws, draws_per_pass, percentile,
-                             channels, labels, uncertainty, prepare_kw, tta, region, tiles_per_pass, overlap, weighting)
+# inference driving (the detect model, ensembles, MC / tiled / scan composition) is inference.py; the names this module always had:
+from .inference import Detector, Ensemble, tta_views  # noqa: E402,F401

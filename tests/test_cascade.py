@@ -94,6 +94,19 @@ def test_cascaded_probabilistic_and_detect_models_match_oracle(dev):
     assert float((got[1].double().cpu() - o["infer_softmax_2"]).abs().max()) < 1e-3
 
 
+def test_inference_stores_nothing_on_the_model(dev):
+    """The stages' output dicts travel by return value: no call of the model or of its detect model adds an attribute to the model."""
+    cfg = O.M1Config(input_spatial_dims=DIMS, filters=C1_FILTERS, strides=C1_STRIDES, dense_skip=True, probabilistic=True,
+                     prob_latent_dims=(3, 2, 1, 0))
+    m = build_m1(cfg, dev, cascaded="noisy-or")
+    m.eval()
+    dm = m.get_detect_model()
+    x = [rnd((2, *DIMS, 3), 45).to(dev), rnd((2, *DIMS, 3), 46).to(dev)]
+    before = set(vars(m))
+    assert len(m(x)) == 4 and len(dm.predict(x)) == 2 and len(dm.predict_mc(x, 2, 2)) == 2
+    assert set(vars(m)) == before and "_last_cascade" not in vars(m)
+
+
 @pytest.mark.parametrize("prob", [False, True])
 def test_standalone_detect_model_matches_oracle(dev, prob):
     """get_detect_model (networks.py:196-206): deterministic -> y_softmax[..., :nc] (deep-supervision heads dropped);

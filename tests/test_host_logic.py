@@ -81,6 +81,36 @@ def test_store_config_args_and_from_config_roundtrip(tmp_path):
         Bad().get_config()
 
 
+def test_detect_model_and_ensemble_are_the_predictors_of_unets_inference():
+    import inspect
+    I = PKG.unets.inference
+    assert N.Ensemble is I.Ensemble and N.tta_views is I.tta_views
+    m = _m1(probabilistic=True, dense_skip=True)
+    dm, other = m.get_detect_model(), m.get_detect_model()
+    assert type(dm) is I.Detector and type(other) is I.Detector and dm is not other
+    assert list(dm.parameters()) == [] == list(dm.children()) and list(dm.buffers()) == [] and dm.state_dict() == {}
+    e = N.Ensemble([m])
+    for name in ("predict_mc", "predict_tiled", "predict_scan"):
+        sigs = [[(p.name, p.kind, p.default) for p in inspect.signature(getattr(who, name)).parameters.values() if p.name != "eps_p"]
+                for who in (dm, e)]
+        assert sigs[0] == sigs[1], name
+    x = torch.zeros(1, 8, 64, 64, 3)
+    for who in (dm, e):
+        with pytest.raises(TypeError):
+            who.predict_mc(x, 2, 1, True)                            # uncertainty is keyword-only, as is everything after draws_per_pass
+        with pytest.raises(TypeError):
+            who.predict_tiled(x, 1, 1, 1, 0.5)                       # ... and after tiles_per_pass
+        with pytest.raises(TypeError):
+            who.predict_scan(x, (3.0, .5, .5), (3.0, .5, .5), 1, 1, None)
+    for bad in (dict(eps_p=None), dict(eps_q=None)):                 # injected draws are the detect model's alone
+        with pytest.raises(TypeError):
+            e.predict(x, **bad)
+        with pytest.raises(TypeError):
+            e.predict(x, tta=("", "w"), **bad)
+    with pytest.raises(TypeError):
+        e.predict_mc(x, 2, eps_p=[torch.zeros(1)])
+
+
 def test_keras_surface_present():
     m = _m1(probabilistic=True, dense_skip=True)
     assert m.output_names == ["detection", "KL"] and m.inputs[0].name == "image"

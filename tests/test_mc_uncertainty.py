@@ -530,6 +530,18 @@ def test_single_member_ensemble_is_the_model_bit_for_bit(two_models):
         m.seed_dropout(82)
         got = NW.Ensemble([m]).predict_mc(x, 4, 2, **kw)
         assert set(got) == set(own) and all(_bits_equal(got[k], own[k]) for k in own) and torch.equal(m.rng_state, st)
+    # every entry point is one body for both: the same call on the detect model and on the ensemble of it, from the same seed
+    calls = (lambda p: p.predict(x), lambda p: p.predict(x, tta=("", "w")),
+             lambda p: p.predict_mc(x, 2, 2, tta=("", "hw"), uncertainty=True, return_samples=True))
+    for i, call in enumerate(calls):
+        m.seed_dropout(84 + i)
+        own = call(m.get_detect_model())
+        own = {k: v.clone() for k, v in own.items()} if isinstance(own, dict) else {"mean": own.clone()}
+        st = m.rng_state.clone()
+        m.seed_dropout(84 + i)
+        got = call(NW.Ensemble([m]))
+        got = got if isinstance(got, dict) else {"mean": got}
+        assert set(got) == set(own) and all(_bits_equal(got[k], own[k]) for k in own) and torch.equal(m.rng_state, st), i
 
 
 @pytest.mark.gpu

@@ -253,6 +253,23 @@ def test_one_tile_is_the_untiled_call_bit_for_bit(models, dev, mode):
         m_.seed_dropout(110)
     got = e.predict_tiled(x, 2, weighting=mode, uncertainty=True)
     assert all(_bits_equal(got[k], want[k]) for k in want) and all(int(m_.rng_state[1]) == 2 for m_ in ms)
+    # a single-member ensemble against its detect model: the tiled and the scan call are one body for both
+    xv = models[1]
+    g = np.random.default_rng(92)
+    raw = torch.from_numpy((g.standard_normal((1, *SCAN, 3)) * 200 + 400).astype(np.float32)).to(dev)
+    calls = (lambda p: p.predict_tiled(xv, tiles_per_pass=GROUP, weighting=mode, uncertainty=True, tta=("", "w")),
+             lambda p: p.predict_scan(raw, SCAN_SP, NET_SP, n_draws=2, percentile=99.5, channels=1, uncertainty=True, region=(5, 44, 20),
+                                      tiles_per_pass=GROUP, weighting=mode))
+    for i, call in enumerate(calls):
+        m.seed_dropout(115 + i)
+        want = {k: ({j: t.clone() for j, t in v.items()} if k == "network" else v.clone()) for k, v in call(dm).items()}
+        state = m.rng_state.clone()
+        m.seed_dropout(115 + i)
+        got = call(NW.Ensemble([m]))
+        assert torch.equal(m.rng_state, state) and int(state[1]) > 0 and set(got) == set(want), i
+        for k in want:
+            pairs = [(got[k][j], want[k][j]) for j in MAPS] if k == "network" else [(got[k], want[k])]
+            assert all(_bits_equal(a, b) for a, b in pairs), (i, k)
 
 
 def _restated(dms, seeders, x, geom, weights, n, R):
