@@ -34,6 +34,21 @@ __device__ __forceinline__ uint4 load_partial_seg(const T* p, int n) {
 
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(unsigned long long)(lptr_t)p; }
 
+// Dynamic LDS of conv_mfma_kernel, defined once for the kernel and its launchers:
+//   [tables TBL_BYTES][KG x pipeline buffers of one K group | epilogue tile (reuses them)][red: NTHR x 2 floats of statistics scratch]
+// The tables come first: they must survive the epilogue tile, which reuses the pipeline buffers.
+template <typename T, int BM, int BN, int KC, int KG>
+struct MfmaLds {
+    static constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64;                      // one 64-byte K-chunk of the A / B tile
+    // rowinfo [BM] int4 + outrow [BM] int, then per member {pointer, C, segments}, then per tap {packed offsets, linear voxel delta}
+    static constexpr int TBL_BYTES = (BM * 20 + M1_MAX_SRC * 16 + 2 * MF_MAX_TAPS * 4 + 15) / 16 * 16;
+    static constexpr int GROUP_BYTES = 2 * KC * (A_BYTES + B_BYTES);                // [2][KC][BM][64] + [2][KC][BN][64] of one K group
+    static constexpr int PIPE_BYTES = GROUP_BYTES * KG;
+    static constexpr int EPI_BYTES = (int)((BM * (BN + MT<T>::SEG) * sizeof(T) + 15) / 16 * 16);
+    static constexpr int RED_OFF = PIPE_BYTES > EPI_BYTES ? PIPE_BYTES : EPI_BYTES;  // `red` behind both, counted from the first group's A tile
+    static constexpr size_t bytes(int nthr) { return (size_t)TBL_BYTES + RED_OFF + (size_t)nthr * 2 * sizeof(float); }
+};
+
 // GLDS = true (every concat member a multiple of one 64-byte K-chunk): both operands go global -> LDS by LDS-DMA
 // (global_load_lds_dwordx4), no staging registers and no ds_write pass -- the VGPR -> LDS store path (<= 85 B/clk/CU)
 // was the bound of the register-staged loop.  The DMA writes lane-linear, so the XOR swizzle is applied on the SOURCE
@@ -50,13 +65,13 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
     static_assert(KG == 1 || GLDS, "K groups: LDS-DMA path only");
     constexpr int SEG = MT<T>::SEG;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
-    constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64;
+    using Lds = MfmaLds<T, BM, BN, KC, KG>;
+    constexpr int A_BYTES = Lds::A_BYTES, B_BYTES = Lds::B_BYTES, TBL_BYTES = Lds::TBL_BYTES, GROUP_BYTES = Lds::GROUP_BYTES;
     constexpr int A_LD = BM * 4 / NTHR;                 // 16-B loads per thread per chunk for A
     constexpr int B_LD = (BN * 4 + NTHR - 1) / NTHR;    // for B
     static_assert((NW == 4 || NW == 8 || NW == 16) && (BM * 4) % NTHR == 0 && BN % 16 == 0, "tile config");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // tables first (they must survive the epilogue tile, which reuses the pipeline buffers)
     int4* rowinfo = reinterpret_cast<int4*>(smem);                                 // [BM] {n, bd, bh, bw}
     int* outrow = reinterpret_cast<int*>(rowinfo + BM);                            // [BM] output voxel index or -1
     const T** s_src = reinterpret_cast<const T**>(outrow + BM);                    // [6]
@@ -64,11 +79,9 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
     int* s_srcSeg = s_srcC + M1_MAX_SRC;                                           // [6]
     int* s_tap = s_srcSeg + M1_MAX_SRC;                                            // [27] packed dd|dh|dw
     int* s_tdl = s_tap + MF_MAX_TAPS;                                              // [27] the same as a linear voxel delta
-    constexpr int TBL_BYTES = (BM * 20 + M1_MAX_SRC * 16 + 2 * MF_MAX_TAPS * 4 + 15) / 16 * 16;
     // (tid, wave: inside the K group -- everything below is group-local; the tables are written by every group with the same values)
     const int kg = KG > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / NTHR) : 0;
     const int tid = KG > 1 ? (int)threadIdx.x - kg * NTHR : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int GROUP_BYTES = 2 * KC * (A_BYTES + B_BYTES);
     unsigned char* A_s = smem + TBL_BYTES + kg * GROUP_BYTES;   // [2][KC][BM][64]
     unsigned char* B_s = A_s + 2 * KC * A_BYTES;         // [2][KC][BN][64]
 
@@ -497,8 +510,7 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
         }
     __syncthreads();
     if (p.stat_partial) {          // per-tile column sums of the stored (rounded) values -> deterministic partials
-        constexpr int EPI_BYTES = (int)((BM * CP * sizeof(T) + 15) / 16 * 16), PIPE_BYTES = 2 * KC * (A_BYTES + B_BYTES) * KG;
-        float* red = reinterpret_cast<float*>(A_s + (PIPE_BYTES > EPI_BYTES ? PIPE_BYTES : EPI_BYTES));   // 2 KB scratch behind both
+        float* red = reinterpret_cast<float*>(A_s + Lds::RED_OFF);   // 2 KB scratch behind both
         constexpr int G = NTHR / BN;                      // row groups
         const int col = tid % BN, rg = tid / BN;
         float s = 0.f, ss = 0.f;
@@ -587,12 +599,7 @@ __global__ void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel(MfmaP p) {
 }
 
 template <typename T, int BM, int BN, int KC, int NTHR, int KG = 1>
-static constexpr size_t mfma_smem_bytes() {
-    size_t tbl = (BM * 20 + M1_MAX_SRC * 16 + 2 * MF_MAX_TAPS * 4 + 15) / 16 * 16;      // = TBL_BYTES of the kernel
-    size_t pipe = (size_t)KC * (2 * BM * 64 + 2 * BN * 64) * KG;
-    size_t epi = ((size_t)BM * (BN + MT<T>::SEG) * sizeof(T) + 15) / 16 * 16;
-    return tbl + (pipe > epi ? pipe : epi) + NTHR * 2 * sizeof(float);
-}
+static constexpr size_t mfma_smem_bytes() { return MfmaLds<T, BM, BN, KC, KG>::bytes(NTHR); }
 
 // ------------------------------------------------------------------------------------------------
 // weight packing:  wp[class][oc][tap_i*CC + c] = w[wtap*wST + c*wSC + (oc+oc_off)*wSO]   (zero padded)

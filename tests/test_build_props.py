@@ -12,7 +12,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-@pytest.mark.parametrize("src", ["wgrad_tf.hip", "wgrad_fold.hip", "wgrad_tap.hip", "conv_halo.hip", "conv_pw.hip"])
+@pytest.mark.parametrize("src", ["wgrad_tf.hip", "wgrad_fold.hip", "wgrad_tap.hip", "conv_halo.hip", "conv_pw.hip", "conv_t3.hip", "conv_mfma.hip"])
 def test_hot_kernels_use_no_scratch_memory(src):
     """A run-time index into a by-value kernel-argument array moves the WHOLE argument struct to scratch (private) memory: every
     p.x becomes a scratch load.  It happened once (`p.Am[mem]` in wgrad_tf_kernel: +10 % per C3 step with the feature off) and is
@@ -65,6 +65,22 @@ def test_cdna4_primitives_are_defined_once():
     cfg = open(os.path.join(CSRC, "config.hip")).read()
     body = cfg[cfg.index("int m1_allow_dynamic_lds("):]
     assert "hipFuncSetAttribute(" in body[:body.index("\n}\n")]
+
+
+def test_conv_mfma_lds_layout_is_defined_once():
+    """conv_mfma_kernel's dynamic-LDS layout (tables, pipeline buffers of the K groups, the epilogue tile that reuses them, the
+    statistics scratch behind both) is written once, in MfmaLds: the kernel takes its offsets from it and the launchers their byte
+    count.  A launcher that restates the table formula by hand drifts from the kernel silently (a too small allocation is an
+    out-of-bounds LDS access, a too large one costs occupancy)."""
+    mfma = [code for _, code in _code_lines(os.path.join(CSRC, "conv_mfma.hip"))]
+    assert sum("BM * 20" in code for code in mfma) == 1, "the table formula is stated once"
+    text = "\n".join(mfma)
+    lds = text[text.index("struct MfmaLds"):]
+    assert "BM * 20" in lds[:lds.index("};")]
+    kernel = text[text.index("void __launch_bounds__(WM * WN * 64 * KG) conv_mfma_kernel"):text.index("mfma_smem_bytes()")]
+    assert "Lds::TBL_BYTES" in kernel and "Lds::RED_OFF" in kernel and "Lds::GROUP_BYTES" in kernel
+    body = text[text.index("mfma_smem_bytes()"):]
+    assert "MfmaLds<" in body[:body.index("}")]
 
 
 def _async_checked_sources():

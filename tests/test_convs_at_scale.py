@@ -473,6 +473,10 @@ EXTRA_CONV_KEYS = [
     ('m1_conv3d_dgrad', 4, 20, 160, 160, (3,), 32, (1, 3, 3), (1, 1, 1), 'bf16', 'need=(1,),acc=(0,)', 'conv_halo:bn16'),
     ('m1_conv3d_fwd', 4, 20, 160, 160, (3,), 32, (1, 3, 3), (1, 1, 1), 'bf16', 'stats=1', 'thin_fwd'),
     ('m1_conv3d_wgrad', 4, 20, 160, 160, (3,), 32, (1, 3, 3), (1, 1, 1), 'bf16', 'acc=1,bias=1,defer=1', 'wgrad_tf'),
+    # InstanceNorm-backward sums from conv_t3's LDS-tile epilogue (no layer of the C3 step: its 3x3x3 layers with a norm in front are
+    # narrower or smaller than the staged-run kernel takes): the smallest launch m1_ct3_plan accepts -- 96 channels on both sides,
+    # N V = 4,200 >= 4,096 voxels -- on a ragged volume (2,100 voxels per sample = 8 tiles of 256 + 52)
+    ('m1_conv3d_dgrad_inbwd', 2, 7, 15, 20, (96,), 96, (3, 3, 3), (1, 1, 1), 'bf16', 'fused=1', 'conv_t3:bn128:ks1'),
 ]
 
 
